@@ -302,9 +302,100 @@ def test_sub_records_arguments():
     assert bench.traffic_key(t) == "tree64:f64:fma:dense:fuse3:sites1048576"
     assert bench.traffic_key(p) == "protein:f64:fma:dense:fuse3:sites262144"
     assert a.workload == "node" and a.steps == 20  # the line's own arguments are untouched
+    # a --steps sized for the 65-us node step: the sub-records keep their own
+    # bounds (a nodes512 step is 512 launches, captured into one graph per lane)
+    big = bench.parse(["--full", "--steps", "15000", "--warmup", "1000"])
+    for kind in ("nodes512", "tree64"):
+        s = bench.sub_args(big, kind)
+        assert (s.steps, s.warmup) == (20, 20), kind
+    for kind in ("protein", "protein_valu", "protein_exact"):
+        s = bench.sub_args(big, kind)
+        assert (s.steps, s.warmup) == (2000, 1000), kind
+    assert big.steps == 15000 and big.warmup == 1000
     b = bench.parse(["--no-tree64", "--no-protein", "--corrupt-rank", "1"])
     assert b.no_tree64 and b.no_protein and b.corrupt_rank == 1
     assert bench.parse([]).corrupt_rank == -1
+
+
+def test_full_is_off_by_default():
+    """A plain invocation asks for the line alone; --full and --dump-outputs parse."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse(["--full", "--dump-outputs", "d"])
+    assert b.full and b.dump_outputs == "d"
+    assert bench.sub_args(b, "tree64").full
+    assert bench._check_word(None).startswith("not run")
+    assert bench._check_word(True) == "ok" and bench._check_word(False) == "CHECK_FAILED"
+
+
+def test_dump_outputs_types_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays as they are, scaler bytes as float32 and
+    integer sums as float64; an entry above its share of the budget keeps the
+    same seeded sorted sites on every call, a list of arrays the same sites
+    of each; the payload stays inside the budget."""
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    n = 1000
+    x3 = rng.random(16 * n)
+    clvs = [rng.random(16 * n).astype(np.float32) for _ in range(3)]
+    sc = rng.integers(0, 2, n).astype(np.uint8)
+    s = np.array([sc.sum()], np.int64)
+    outs = [("x3", x3, 16), ("clv", clvs, 16), ("scaler", sc, 1), ("scaler_sum", s, 1)]
+    w = bench.dump_outputs(tmp_path / "a", outs)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert np.array_equal(got["x3"], x3) and got["x3"].dtype == np.float64
+    assert got["clv"].shape == (3, 16 * n) and got["clv"].dtype == np.float32
+    assert got["scaler"].dtype == np.float32 and np.array_equal(got["scaler"], sc)
+    assert got["scaler_sum"].dtype == np.float64 and got["scaler_sum"].tolist() == [float(s[0])]
+    assert w["x3"] == [[16 * n], "float64"]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 16 * 8 * 100)  # 100 f64 sites per entry
+    bench.dump_outputs(tmp_path / "b", outs)
+    import torch
+
+    touts = [(k, [torch.from_numpy(x) for x in v] if isinstance(v, list) else torch.from_numpy(v), w_)
+             for k, v, w_ in outs]  # tensors, as the GPU workloads pass them
+    bench.dump_outputs(tmp_path / "c", touts, rank=1)
+    got = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    again = {p.name: np.load(p) for p in (tmp_path / "c").iterdir()}
+    assert sorted(again) == ["clv.rank1.npy", "scaler.rank1.npy", "scaler_sum.rank1.npy", "x3.rank1.npy"]
+    idx = bench.dump_sample_sites(n, 100)
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(got["x3"], x3.reshape(-1, 16)[idx])
+    assert all(np.array_equal(got[k], again[f"{k}.rank1.npy"]) and got[k].dtype == again[f"{k}.rank1.npy"].dtype
+               for k in got)
+    cidx = bench.dump_sample_sites(n, 66)  # 3 f32 arrays share one entry's budget
+    assert got["clv"].shape == (3, 66, 16)
+    assert all(np.array_equal(got["clv"][j], clvs[j].reshape(-1, 16)[cidx]) for j in range(3))
+    assert np.array_equal(got["scaler"], sc)  # under its share: whole
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET
+    assert np.array_equal(bench.dump_sample_sites(5, 9), np.arange(5))
+
+
+def test_swemu_plain_run_dumps_outputs(oracle, tmp_path):
+    """bench.py --workload swemu1024 (no GPU) as a plain run: --steps timed
+    steps, no check, one line with ms_per_step, and the dumped x3 / scaler
+    bytes equal the oracle's on the same seeded inputs; --full checks it."""
+    import json
+
+    import numpy as np
+
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", "swemu1024", "--steps", "2", "--warmup", "1"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       timeout=120, env=_env(), cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["check"].startswith("not run")
+    h = oracle.gen_hostmem(1024, np.float64, bench.SEED)
+    e3, esc, _ = oracle.plf(h["x1"], h["x2"], h["EV"], h["left"], h["right"], h["wgt"])
+    assert np.array_equal(np.load(tmp_path / "x3.npy").view(np.uint64), e3.view(np.uint64))
+    assert np.array_equal(np.load(tmp_path / "scaler.npy"), esc.astype(np.float32))
+    r = subprocess.run(cmd + ["--full"], capture_output=True, text=True, timeout=120, env=_env(),
+                       cwd=str(ROOT))
+    assert r.returncode == 0 and json.loads(r.stdout.splitlines()[-1])["check"] == "ok"
 
 
 def test_common_start_only_on_one_node():

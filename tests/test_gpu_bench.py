@@ -16,8 +16,8 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def _bench(*args, expect_rc=0):
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-           "--buffer-sets", "2", *args]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1",
+           "--no-cpu-baseline", "--buffer-sets", "2", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(ROOT))
     assert r.returncode == expect_rc, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -94,3 +94,40 @@ def test_sweep_small_sites_one_and_two_lanes():
     assert d["check"] == "ok" and [row["sites"] for row in d["rows"]] == [1, 1000, 65537]
     for row in d["rows"]:
         assert row["check"] == "ok" and 0 < row["graph_two_lanes_us_per_call"] and 0 < row["graph_us_per_call"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(oracle, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, checks and measures
+    nothing else, and --dump-outputs writes what the last timed step computed:
+    step warmup + steps - 1 = 4 ran on buffer set 4 % 3 = 1, whose inputs are
+    the host_mem protocol's of seed SEED + 1, so x3, the scaler bytes and the
+    scaler sum equal the oracle's bit for bit."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    n = 4099
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+           "--buffer-sets", "3", "--sites", str(n), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(ROOT))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["metric"] == bench.METRIC and d["unit"] == "sites/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3))
+    assert d["check"].startswith("not run") and d["cpu_baseline"] is None
+    assert "host_buffers" not in d and "traffic" not in d["roofline"]
+    assert "frac_second_region" not in d["roofline"] and d["roofline"]["frac"] > 0
+    assert not {"nodes512", "tree64", "protein", "check_windows", "lnl_per_rank"} & set(d["config"])
+    h = oracle.gen_hostmem(n, np.float64, bench.SEED + 1)
+    e3, esc, einc = oracle.plf(h["x1"], h["x2"], h["EV"], h["left"], h["right"], h["wgt"])
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["scaler.npy", "scaler_sum.npy", "x3.npy"]
+    assert got["x3.npy"].dtype == np.float64 and got["scaler.npy"].dtype == np.float32
+    assert np.array_equal(got["x3.npy"].view(np.uint64), e3.view(np.uint64))
+    assert np.array_equal(got["scaler.npy"], esc.astype(np.float32))
+    assert got["scaler_sum.npy"].tolist() == [float(einc)]
+    assert d["dumped_outputs"]["x3"] == [[16 * n], "float64"]

@@ -47,7 +47,7 @@ def _torchrun(nproc, args, env, timeout=300):
 
 def _bench(nproc, backend, *extra):
     args = ["--gpus", str(nproc), "--workload", "nodes512", "--nodes", str(NODES), "--sites",
-            str(SITES), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra]
+            str(SITES), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra]
     env = {**os.environ, "PLFX_DIST_BACKEND": backend, "OMP_NUM_THREADS": "4"}
     r = _torchrun(nproc, args, env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -105,7 +105,7 @@ def test_nodes_three_ranks_ragged_split():
     one = _bench(1, "gloo")
     assert three["config"]["lnl_all_nodes_all_ranks"] == one["config"]["lnl_all_nodes_all_ranks"]
     assert three["config"]["scaler_events_all_ranks"] == one["config"]["scaler_events_all_ranks"]
-    r = _torchrun(2, ["--gpus", "2", "--sites", "65536", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = _torchrun(2, ["--gpus", "2", "--sites", "65536", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
                       "--buffer-sets", "2", "--no-nodes512"],
                   {**os.environ, "PLFX_DIST_BACKEND": "gloo", "OMP_NUM_THREADS": "4"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -124,7 +124,7 @@ def test_bench_gpus_two_without_outer_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PLFX_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--sites", "65536", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--buffer-sets", "2", "--nodes", "12"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--buffer-sets", "2", "--nodes", "12"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(ROOT), env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -224,7 +224,8 @@ def test_eight_ranks_gloo_rehearsal():
     in the one all-reduce, the scaler totals exact, value_device >= value,
     and the nodes512 job lnL equal to one rank's bit for bit."""
     def run(nproc, *args):
-        r = _torchrun(nproc, ["--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *args],
+        r = _torchrun(nproc, ["--gpus", str(nproc), "--full", "--steps", "3", "--warmup", "1",
+                              "--no-cpu-baseline", *args],
                       {**os.environ, "PLFX_DIST_BACKEND": "gloo", "OMP_NUM_THREADS": "2"})
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -261,7 +262,7 @@ def test_corrupted_rank_fails_every_check():
     after each timed region) turns the line red at world 2: exit 3,
     `check` CHECK_FAILED, and exactly one mismatched window in the node line
     and in each sub-record."""
-    r = _torchrun(2, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sites", "65536",
+    r = _torchrun(2, ["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sites", "65536",
                       "--buffer-sets", "2", "--nodes", "4", "--corrupt-rank", "1"],
                   {**os.environ, "PLFX_DIST_BACKEND": "gloo", "OMP_NUM_THREADS": "4"})
     assert r.returncode != 0, r.stdout[-3000:]

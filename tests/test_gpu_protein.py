@@ -498,7 +498,7 @@ def test_bench_prottree64_small(tips):
 
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, str(root / "bench.py"), "--workload", "prottree64", "--sites", "4099",
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--no-second-region"] + \
+           "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--no-second-region"] + \
         (["--tips"] if tips else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(root))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

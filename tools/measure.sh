@@ -30,7 +30,7 @@ small() {  # copy a file to OUT if it is under 8 MB
   return 0
 }
 cd $R
-step bench 400 python -u $R/bench.py "$@"
+step bench 400 python -u $R/bench.py --full "$@"
 cd /tmp && export TMPDIR=/tmp
 step trace 400 rocprofv3 --kernel-trace --stats -T -d $TMPP/trace -o run --output-format csv -- python3 $R/bench.py "$@" --no-cpu-baseline --no-nodes512 --no-tree64 --no-protein
 step fetch 400 rocprofv3 --pmc FETCH_SIZE -T -d $TMPP/fetch -o run --output-format csv -- python3 $R/bench.py "$@" --no-cpu-baseline --no-nodes512 --no-tree64 --no-protein --no-second-region --steps $P --warmup 2 --launch bound
