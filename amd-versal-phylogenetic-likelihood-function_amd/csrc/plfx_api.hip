@@ -14,7 +14,6 @@
 #include <deque>
 #include <new>
 #include <string>
-#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -22,6 +21,7 @@
 #include "../../include/plfx.h"
 #include "plf_kernels.hpp"
 #include "testbench.hpp"
+#include "trav_plan.hpp"
 
 constexpr int kHostChunksMax = 16;
 
@@ -467,6 +467,65 @@ size_t clv_bytes_of(int dtype, int states, int64_t n) {
   return (size_t)(n > 0 ? n : 0) * 4 * states * (dtype == PLFX_F32 ? 4 : 8);
 }
 
+// n == 0: nothing is launched; the count scaler sums at sums (may be NULL) are zero
+int zero_sums(plfx_ctx *ctx, hipStream_t s, int64_t *sums, int count) {
+  if (sums && count > 0) PLFX_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)count * sizeof(int64_t), s));
+  return PLFX_OK;
+}
+
+// The arrays of a traversal call (plfx_traverse_tips): its ops as node descriptors.
+struct TravNodes {
+  const plfx_trav_op *ops;
+  void *const *clv;
+  const uint8_t *const *tips;  // may be NULL
+  const char *pmats;
+  size_t mat_bytes;  // of one matrix (C*S*S values)
+  uint8_t *const *scalers;
+  int64_t *scaler_sums;
+  // the node descriptor of op j, tip child first (dense/tip runs as tip/dense:
+  // the product u1*u2 commutes exactly); *kind = number of tip children
+  plfx_node node(int j, int *kind) const {
+    const plfx_trav_op &o = ops[j];
+    const bool t1 = tips && tips[o.child1], t2 = tips && tips[o.child2];
+    plfx_node nd{t1 ? (const void *)tips[o.child1] : clv[o.child1],
+                 t2 ? (const void *)tips[o.child2] : clv[o.child2], clv[o.parent],
+                 pmats + (size_t)(2 * o.pmat) * mat_bytes, pmats + (size_t)(2 * o.pmat + 1) * mat_bytes,
+                 scalers ? scalers[j] : nullptr, scaler_sums ? scaler_sums + j : nullptr};
+    if (!t1 && t2) {
+      std::swap(nd.x1, nd.x2);
+      std::swap(nd.left, nd.right);
+    }
+    *kind = (t1 ? 1 : 0) + (t2 ? 1 : 0);
+    return nd;
+  }
+};
+
+// The descriptor of a fused pass (DeepDescH, SeptetDescH) over the ops ids[0..count),
+// each checked as a node; the first `leaves` of them are the leaf ops, whose
+// children are the pass's inputs g.  A septet's leaf ops come tip child first
+// (node()); a deep pass's leaves are all dense or all tips, so there child1,
+// child2 stay as the op names them.
+template <typename Desc>
+int fill_fused(plfx_ctx *ctx, const TravNodes &tn, const int *ids, int count, int leaves, int64_t n,
+               size_t clv_bytes, Desc *d) {
+  for (int q = 0; q < count; q++) {
+    int kq;
+    const plfx_node nd = tn.node(ids[q], &kq);
+    const int rc = check_node(ctx, nd, kq, n, ids[q], clv_bytes);
+    if (rc != PLFX_OK) return rc;
+    if (q < leaves) {
+      d->g[2 * q] = nd.x1;
+      d->g[2 * q + 1] = nd.x2;
+    }
+    d->x[q] = nd.x3;
+    d->mat[2 * q] = nd.left;
+    d->mat[2 * q + 1] = nd.right;
+    d->sc[q] = nd.scaler;
+    d->ss[q] = nd.scaler_sum;
+  }
+  return PLFX_OK;
+}
+
 // A tip/tip protein node whose values sit in its stream's combination tables
 // after batch_impl: its CLV (x3), its table and its two tip-code arrays.
 struct TabRef {
@@ -491,8 +550,8 @@ int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, cons
   for (int i = 0; i < count; i++) {
     const plfx_node &d = nodes[i];
     int rc = check_node(ctx, d, tips, n, ids ? ids[i] : i, clv_bytes_of(dtype, states, n));
+    if (rc == PLFX_OK && n == 0) rc = zero_sums(ctx, s, d.scaler_sum, 1);
     if (rc != PLFX_OK) return rc;
-    if (n == 0 && d.scaler_sum) PLFX_HIP(ctx, hipMemsetAsync(d.scaler_sum, 0, sizeof(int64_t), s));
   }
   if (n == 0 || count == 0) return PLFX_OK;
   PLFX_WS(ctx, s, w);
@@ -982,171 +1041,34 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   if (flags & ~PLFX_FMA) return fail(ctx, PLFX_ERR_INVALID, "bad flags %d", flags);
   if (nops < 0 || (nops > 0 && (!ops || !clv || !pmats || !EV)))
     return fail(ctx, PLFX_ERR_INVALID, "bad traverse arguments");
-  const size_t es = dtype == PLFX_F32 ? 4 : 8;
-  const size_t mat = (size_t)states * states * 4;  // C*S*S values per matrix
-  const size_t cb = clv_bytes_of(dtype, states, n);
-  auto is_tip = [&](int sl) { return tips && tips[sl]; };
-  // dependency levels: RAW on children (cdep), WAR/WAW on the parent slot (pdep)
-  std::vector<int> level(nops, 0), pdep(nops, 0), w1(nops, -1), w2(nops, -1);
-  std::vector<int> slot_write(nslots, -1), slot_read(nslots, -1), last_writer(nslots, -1);
-  int nlev = 0;
-  for (int j = 0; j < nops; j++) {
-    const plfx_trav_op &o = ops[j];
-    if (o.parent < 0 || o.parent >= nslots || o.child1 < 0 || o.child1 >= nslots || o.child2 < 0 ||
-        o.child2 >= nslots || o.pmat < 0 || o.pmat >= npmats)
-      return fail(ctx, PLFX_ERR_INVALID, "op %d: slot/pmat index out of range", j);
-    if (o.parent == o.child1 || o.parent == o.child2)
-      return fail(ctx, PLFX_ERR_INVALID, "op %d: parent slot aliases a child", j);
-    if (is_tip(o.parent)) return fail(ctx, PLFX_ERR_INVALID, "op %d: parent slot is a tip", j);
-    int cdep = 0, pd = 0;
-    for (int sl : {o.child1, o.child2})
-      if (slot_write[sl] >= 0) cdep = std::max(cdep, slot_write[sl] + 1);
-    if (slot_write[o.parent] >= 0) pd = std::max(pd, slot_write[o.parent] + 1);
-    if (slot_read[o.parent] >= 0) pd = std::max(pd, slot_read[o.parent] + 1);
-    const int lv = std::max(cdep, pd);
-    level[j] = lv;
-    pdep[j] = pd;
-    w1[j] = last_writer[o.child1];
-    w2[j] = last_writer[o.child2];
-    slot_write[o.parent] = lv;
-    last_writer[o.parent] = j;
-    for (int sl : {o.child1, o.child2}) slot_read[sl] = std::max(slot_read[sl], lv);
-    nlev = std::max(nlev, lv + 1);
-  }
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  // plan: levels and fused groups from the op list and the tip slots alone
+  std::vector<unsigned char> tip_mask;
+  if (nops > 0 && tips)
+    for (int sl = 0; sl < nslots; sl++) tip_mask.push_back(tips[sl] != nullptr);
+  plfx::TravPlan plan;
+  std::string plan_err;
+  if (plfx::plan_traversal(ops, nops, nslots, npmats, tip_mask.empty() ? nullptr : tip_mask.data(),
+                           states, ctx->fuse, &plan, &plan_err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", plan_err.c_str());
+  int sched[PLFX_SCHED_COUNTS] = {};  // as plfx_traverse_schedule reports it; [6]: launches
+  std::copy(plan.counts, plan.counts + 6, sched);
   hipStream_t s = pick(ctx, stream);
+  if (n == 0) {  // nothing to launch
+    const int rc = zero_sums(ctx, s, scaler_sums, nops);
+    if (rc != PLFX_OK) return rc;
+    std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
+    return PLFX_OK;
+  }
   unsigned long long *ws = nullptr;
-  if (nops > 0 && n > 0) {
+  if (nops > 0) {
     PLFX_WS(ctx, s, w);
     ws = w->ws;
   }
-  const char *pm = static_cast<const char *>(pmats);
-  // the node descriptor of op j, tip child first (dense/tip runs as tip/dense:
-  // the product u1*u2 commutes exactly); *kind = number of tip children
-  auto node_of = [&](int j, int *kind) {
-    const plfx_trav_op &o = ops[j];
-    const bool t1 = is_tip(o.child1), t2 = is_tip(o.child2);
-    plfx_node nd{t1 ? (const void *)tips[o.child1] : clv[o.child1],
-                 t2 ? (const void *)tips[o.child2] : clv[o.child2], clv[o.parent],
-                 pm + (size_t)(2 * o.pmat) * mat * es, pm + (size_t)(2 * o.pmat + 1) * mat * es,
-                 scalers ? scalers[j] : nullptr, scaler_sums ? scaler_sums + j : nullptr};
-    if (!t1 && t2) {
-      std::swap(nd.x1, nd.x2);
-      std::swap(nd.left, nd.right);
-    }
-    *kind = (t1 ? 1 : 0) + (t2 ? 1 : 0);
-    return nd;
-  };
-  // Fused level pairs (DNA): op P whose two children were last written by
-  // ops A, B of the level just below it, with the same tip kind, and whose own
-  // slot is free by then (pdep <= level of A), runs with A and B in one pass
-  // (plf_dna.hpp TripleDesc): A's and B's CLVs are written but not read back.
-  struct Triple {
-    int a, b, p, kind;
-  };
-  std::vector<Triple> triples;
-  std::vector<char> used(nops, 0);
-  // Fused three-level subtrees (DNA, plf_dna.hpp SeptetDesc): root R two
-  // levels above four ops A of one tip kind, through the two ops B that R's
-  // children were last written by; R's and the B's slots free by level L.
-  // Ordered so that a[2i], a[2i+1] are b[i]'s child1, child2 and b[0], b[1]
-  // are R's.  Tried first; the remaining ops form triples.
-  struct Septet {
-    int a[4], b[2], r, kind;
-  };
-  std::vector<Septet> septets;
-  auto fusible_pair = [&](int p, int L, int &x, int &y) {  // p's writers at level L
-    x = w1[p];
-    y = w2[p];
-    return x >= 0 && y >= 0 && x != y && !used[x] && !used[y] && !used[p] && level[x] == L &&
-           level[y] == L && level[p] == L + 1;
-  };
-  // Fused deep subtrees (DNA, plf_dna.hpp DeepDesc): a complete binary
-  // subtree of depth D = 6, 5 or 4 (2^D - 1 ops on consecutive levels
-  // L..L+D-1), every op's own slot free by L (pdep <= L), all leaves dense
-  // or all leaves tips.  Collected per level in heap
-  // order (children left to right before parents): the ops of level k are
-  // lv[k], and lv[k][i]'s children were written by lv[k-1][2i], lv[k-1][2i+1].
-  // Tried before the three-level subtrees.
-  struct Deep {
-    std::vector<int> ops;  // the 2^D - 1 ops in DeepDesc node order
-    int L, D, tips;        // tips: 0 dense leaves, 2 every leaf a tip
-  };
-  std::vector<Deep> deeps;
-  std::function<bool(int, int, int, std::vector<int> *)> complete =
-      [&](int r, int D, int L, std::vector<int> *lv) {
-        if (r < 0 || used[r] || level[r] != L + D - 1 || pdep[r] > L) return false;
-        if (D > 1 && (w1[r] < 0 || w2[r] < 0 || w1[r] == w2[r] ||
-                      !complete(w1[r], D - 1, L, lv) || !complete(w2[r], D - 1, L, lv)))
-          return false;
-        lv[D - 1].push_back(r);
-        return true;
-      };
-  if (ctx->fuse >= 3 && states == 4) {
-    for (int D = 6; D >= 4; D--) {  // deepest first
-      for (int r = 0; r < nops; r++) {
-        if (level[r] < D - 1 || used[r]) continue;
-        std::vector<int> lv[6];
-        if (!complete(r, D, level[r] - (D - 1), lv)) continue;
-        // every leaf dense, or every leaf a tip (the coded-leaf pass's
-        // tables); mixed leaves stay with the three-level passes
-        bool dense = true, coded = true;
-        for (int j : lv[0]) {
-          const bool t1 = is_tip(ops[j].child1), t2 = is_tip(ops[j].child2);
-          dense = dense && !t1 && !t2;
-          coded = coded && t1 && t2;
-        }
-        // nor may a deep pass take the top of a subtree whose lower levels are
-        // still unfused (over coded leaves: the septets below it would become
-        // level pairs and move more bytes in all)
-        for (int j : lv[0])
-          for (int wr : {w1[j], w2[j]})
-            if (wr >= 0 && !used[wr] && level[wr] == level[r] - D) dense = coded = false;
-        if (!dense && !coded) continue;
-        Deep t{{}, level[r] - (D - 1), D, coded ? 2 : 0};
-        for (int k = 0; k < D; k++) t.ops.insert(t.ops.end(), lv[k].begin(), lv[k].end());
-        for (int j : t.ops) used[j] = 1;
-        deeps.push_back(std::move(t));
-      }
-    }
-  }
-  if (ctx->fuse >= 2 && states == 4) {
-    for (int r = 0; r < nops; r++) {
-      Septet t{};
-      t.r = r;
-      const int L = level[r] - 2;
-      if (L < 0 || used[r] || pdep[r] > L) continue;
-      if (!fusible_pair(r, L + 1, t.b[0], t.b[1])) continue;
-      if (pdep[t.b[0]] > L || pdep[t.b[1]] > L) continue;
-      if (!fusible_pair(t.b[0], L, t.a[0], t.a[1]) || !fusible_pair(t.b[1], L, t.a[2], t.a[3]))
-        continue;
-      int k[4];
-      for (int i = 0; i < 4; i++) node_of(t.a[i], &k[i]);
-      if (k[1] != k[0] || k[2] != k[0] || k[3] != k[0]) continue;
-      t.kind = k[0];
-      for (int j : {t.a[0], t.a[1], t.a[2], t.a[3], t.b[0], t.b[1], r}) used[j] = 1;
-      septets.push_back(t);
-    }
-  }
-  if (ctx->fuse >= 1 && states == 4) {
-    for (int p = 0; p < nops; p++) {
-      const int a = w1[p], b = w2[p];
-      if (a < 0 || b < 0 || a == b || used[a] || used[b] || used[p]) continue;
-      const int L = level[a];
-      if (level[b] != L || level[p] != L + 1 || pdep[p] > L) continue;
-      int ka, kb;
-      node_of(a, &ka);
-      node_of(b, &kb);
-      if (ka != kb) continue;
-      used[a] = used[b] = used[p] = 1;
-      triples.push_back({a, b, p, ka});
-    }
-  }
-  // the schedule, as plfx_traverse_schedule reports it
-  int sched[PLFX_SCHED_COUNTS] = {};
-  for (const Deep &t : deeps) sched[6 - t.D]++;
-  sched[3] = (int)septets.size();
-  sched[4] = (int)triples.size();
-  for (int j = 0; j < nops; j++) sched[5] += used[j] ? 0 : 1;
+  const size_t cb = clv_bytes_of(dtype, states, n);
+  const TravNodes tn{ops, clv, tips, static_cast<const char *>(pmats),
+                     (size_t)states * states * 4 * (dtype == PLFX_F32 ? 4 : 8), scalers, scaler_sums};
+  // execute: level by level, the level's fused groups first
   std::vector<plfx_node> batch[3];  // by number of tip children
   std::vector<int> bop[3];           // the op index of each batch entry
   std::vector<plfx::TripleDescH> tb[3];
@@ -1157,97 +1079,58 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   // reading the children's CLVs back from HBM.  Only for the next level: later
   // levels may overwrite the tables or the children's slots.
   std::vector<TabRef> prev_tabs, cur_tabs;
-  const bool tab_mode = states == 20 && n > 0;
-  for (int lv = 0; lv < nlev; lv++) {
+  const bool tab_mode = states == 20;
+  for (int lv = 0; lv < plan.nlev; lv++) {
     for (int k = 0; k < 3; k++) {
       batch[k].clear();
       bop[k].clear();
       tb[k].clear();
       sb[k].clear();
     }
-    for (const Deep &t : deeps) {
-      if (t.L != lv) continue;
-      plfx::DeepDescH d{};
-      const int nodes = (1 << t.D) - 1, leaf_ops = 1 << (t.D - 1);
-      for (int q = 0; q < nodes; q++) {
-        const int j = t.ops[q];
-        const plfx_trav_op &o = ops[j];
-        int kq;
-        const int rc = check_node(ctx, node_of(j, &kq), kq, n, j, cb);
+    // plan.groups holds the deep passes, then the septets, then the triples
+    for (const plfx::TravGroup &g : plan.groups) {
+      if (g.level != lv) continue;
+      if (g.kind == plfx::kTravSeptet) {
+        plfx::SeptetDescH d{};
+        const int rc = fill_fused(ctx, tn, g.ops.data(), 7, 4, n, cb, &d);
         if (rc != PLFX_OK) return rc;
-        if (q < leaf_ops) {  // level 1: the leaves (CLVs or tip codes), child1 then child2
-          d.g[2 * q] = t.tips ? (const void *)tips[o.child1] : clv[o.child1];
-          d.g[2 * q + 1] = t.tips ? (const void *)tips[o.child2] : clv[o.child2];
-        }
-        d.x[q] = clv[o.parent];
-        d.mat[2 * q] = pm + (size_t)(2 * o.pmat) * mat * es;
-        d.mat[2 * q + 1] = pm + (size_t)(2 * o.pmat + 1) * mat * es;
-        d.sc[q] = scalers ? scalers[j] : nullptr;
-        d.ss[q] = scaler_sums ? scaler_sums + j : nullptr;
-      }
-      if (n == 0) {
-        for (int64_t *ss : d.ss)
-          if (ss) PLFX_HIP(ctx, hipMemsetAsync(ss, 0, sizeof(int64_t), s));
-        continue;
-      }
-      hipError_t e = plfx::launch_plf_dna_deep(dtype, t.D, &d, EV, wgt, n, ws, ctx->max_blocks, s,
-                                               t.tips, tipvec);
-      if (e != hipSuccess) return hip_fail(ctx, e, "fused deep-subtree launch");
-      sched[6]++;
-    }
-    for (const Septet &t : septets) {
-      if (level[t.a[0]] != lv) continue;
-      const int id[7] = {t.a[0], t.a[1], t.a[2], t.a[3], t.b[0], t.b[1], t.r};
-      plfx::SeptetDescH d{};
-      for (int q = 0; q < 7; q++) {
-        int kq;
-        const plfx_node nd = node_of(id[q], &kq);
-        const int rc = check_node(ctx, nd, kq, n, id[q], cb);
+        sb[g.tips].push_back(d);
+      } else if (g.kind == plfx::kTravTriple) {
+        const int a = g.ops[0], b = g.ops[1], p = g.ops[2];
+        int ka, kb, kp;
+        const plfx_node A = tn.node(a, &ka), B = tn.node(b, &kb), P = tn.node(p, &kp);
+        for (int rc : {check_node(ctx, A, ka, n, a, cb), check_node(ctx, B, kb, n, b, cb),
+                       check_node(ctx, P, kp, n, p, cb)})
+          if (rc != PLFX_OK) return rc;
+        // P's children as op P names them: child1 = A's slot or B's slot
+        const bool a_first = ops[p].child1 == ops[a].parent;
+        const plfx_node &F = a_first ? A : B, &G = a_first ? B : A;
+        tb[g.tips].push_back(plfx::TripleDescH{
+            F.x1, F.x2, G.x1, G.x2, F.x3, G.x3, P.x3, (const double *)F.left,
+            (const double *)F.right, (const double *)G.left, (const double *)G.right,
+            (const double *)P.left, (const double *)P.right, F.scaler, G.scaler, P.scaler,
+            F.scaler_sum, G.scaler_sum, P.scaler_sum});
+      } else {  // a deep pass: one launch each, ahead of the level's other work
+        const int D = 6 - g.kind;
+        plfx::DeepDescH d{};
+        const int rc = fill_fused(ctx, tn, g.ops.data(), (1 << D) - 1, 1 << (D - 1), n, cb, &d);
         if (rc != PLFX_OK) return rc;
-        if (q < 4) {
-          d.g[2 * q] = nd.x1;
-          d.g[2 * q + 1] = nd.x2;
-        }
-        d.x[q] = nd.x3;
-        d.mat[2 * q] = nd.left;
-        d.mat[2 * q + 1] = nd.right;
-        d.sc[q] = nd.scaler;
-        d.ss[q] = nd.scaler_sum;
+        hipError_t e = plfx::launch_plf_dna_deep(dtype, D, &d, EV, wgt, n, ws, ctx->max_blocks, s,
+                                                 g.tips, tipvec);
+        if (e != hipSuccess) return hip_fail(ctx, e, "fused deep-subtree launch");
+        sched[6]++;
       }
-      sb[t.kind].push_back(d);
-    }
-    for (const Triple &t : triples) {
-      if (level[t.a] != lv) continue;
-      int ka, kb, kp;
-      const plfx_node A = node_of(t.a, &ka), B = node_of(t.b, &kb), P = node_of(t.p, &kp);
-      for (int rc : {check_node(ctx, A, ka, n, t.a, cb), check_node(ctx, B, kb, n, t.b, cb),
-                     check_node(ctx, P, kp, n, t.p, cb)})
-        if (rc != PLFX_OK) return rc;
-      // P's children as op P names them: child1 = A's slot or B's slot
-      const bool a_first = ops[t.p].child1 == ops[t.a].parent;
-      const plfx_node &F = a_first ? A : B, &G = a_first ? B : A;
-      tb[t.kind].push_back(plfx::TripleDescH{
-          F.x1, F.x2, G.x1, G.x2, F.x3, G.x3, P.x3, (const double *)F.left,
-          (const double *)F.right, (const double *)G.left, (const double *)G.right,
-          (const double *)P.left, (const double *)P.right, F.scaler, G.scaler, P.scaler,
-          F.scaler_sum, G.scaler_sum, P.scaler_sum});
     }
     for (int j = 0; j < nops; j++) {
-      if (level[j] != lv || used[j]) continue;
+      if (plan.level[j] != lv || plan.fused[j]) continue;
       int kind;
-      const plfx_node nd = node_of(j, &kind);
+      const plfx_node nd = tn.node(j, &kind);
       batch[kind].push_back(nd);
       bop[kind].push_back(j);
     }
     for (int k = 0; k < 3; k++) {
       for (size_t i = 0; i < sb[k].size(); i += plfx::kMaxSeptets) {
         const int c = (int)std::min<size_t>(plfx::kMaxSeptets, sb[k].size() - i);
-        if (n == 0) {
-          for (int q = 0; q < c; q++)
-            for (int64_t *ss : sb[k][i + q].ss)
-              if (ss) PLFX_HIP(ctx, hipMemsetAsync(ss, 0, sizeof(int64_t), s));
-          continue;
-        }
         hipError_t e = plfx::launch_plf_dna_septets(dtype, sb[k].data() + i, c, EV, wgt, n,
                                                     ws, ctx->max_blocks, s, k, tipvec);
         if (e != hipSuccess) return hip_fail(ctx, e, "fused three-level launch");
@@ -1255,12 +1138,6 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
       }
       for (size_t i = 0; i < tb[k].size(); i += plfx::kMaxTriples) {
         const int c = (int)std::min<size_t>(plfx::kMaxTriples, tb[k].size() - i);
-        if (n == 0) {
-          for (int q = 0; q < c; q++)
-            for (int64_t *ss : {tb[k][i + q].ssa, tb[k][i + q].ssb, tb[k][i + q].ssp})
-              if (ss) PLFX_HIP(ctx, hipMemsetAsync(ss, 0, sizeof(int64_t), s));
-          continue;
-        }
         hipError_t e = plfx::launch_plf_dna_triples(dtype, tb[k].data() + i, c, EV, wgt, n, ws,
                                                     ctx->max_blocks, s, k, tipvec);
         if (e != hipSuccess) return hip_fail(ctx, e, "fused level-pair launch");

@@ -141,6 +141,25 @@ def test_traverse_rejects_bad_ops(ctx):
             ctx.traverse(np.array(bad, np.int32), clv, pm, EV, n)
 
 
+def test_traverse_rejects_negative_n(ctx, oracle):
+    """n < 0 is refused before anything is launched, fused groups included (an
+    8-taxon tree is one three-level pass): nothing is written."""
+    import plfx
+    import torch
+
+    ops = oracle.balanced_tree_ops(8)
+    clv = [torch.full((16 * 8,), 3.0, dtype=torch.float64, device="cuda") for _ in range(15)]
+    pm = torch.ones(7 * 128, dtype=torch.float64, device="cuda")
+    EV = torch.ones(16, dtype=torch.float64, device="cuda")
+    sums = torch.full((7,), -7, dtype=torch.int64, device="cuda")
+    with pytest.raises(plfx.PlfxError, match="n < 0") as e:
+        ctx.traverse(ops, clv, pm, EV, -1, None, None, sums)
+    assert e.value.code == plfx.ERR_INVALID
+    torch.cuda.synchronize()
+    assert ctx.last_schedule() == dict.fromkeys(plfx.SCHED_KEYS, 0)
+    assert all(bool((t == 3.0).all()) for t in clv) and bool((sums == -7).all())
+
+
 def test_tree64_full_size_window(ctx, oracle):
     """BASELINE config 3 shape: 64-taxon balanced tree, 63 inner nodes, 2^20
     sites, f64, on the GPU; sites are independent, so a 4096-site window is
@@ -532,6 +551,72 @@ def test_fused_depth4_depth5_subtrees(oracle, tipmode, dtype, monkeypatch):
     assert np.array_equal(sums.cpu().numpy(), esums)
     for j in range(nops):
         assert np.array_equal(scal[j].cpu().numpy(), escal[j]), j
+
+
+def _run_schedule_case(oracle, tree, mode, fuse, monkeypatch):
+    """One traversal (f64, 33 sites, sums and scaler bytes) of a tree of
+    tests/test_trav_plan.py under PLFX_FUSE=fuse, checked bit for bit against
+    the oracle; returns Context.last_schedule()."""
+    import plfx
+    import torch
+    from test_trav_plan import _mask, _tree
+
+    n, dtype = 33, np.float64
+    ops, nslots, ntax = _tree(tree)
+    nops = ops.shape[0]
+    is_coded = _mask(nslots, ntax, mode)[:ntax]
+    rng = np.random.default_rng(77)
+    codes = [oracle.random_tip_codes(rng, n, 0.2) for _ in range(ntax)]
+    dense = [rng.random(16 * n).astype(dtype) for _ in range(ntax)]
+    pm = (rng.random(nops * 128) * 0.3).astype(dtype)
+    EV = (rng.random(16) * 0.3).astype(dtype)
+    wgt = rng.integers(1, 5, n).astype(np.int32)
+    host = [oracle.expand_tips(codes[t], dtype) if is_coded[t] else dense[t].copy() for t in range(ntax)]
+    host += [np.zeros(16 * n, dtype) for _ in range(nslots - ntax)]
+    esums, escal = oracle.traverse(4, 4, ops, host, pm, EV, n, wgt, want_scalers=True)
+    assert esums.sum() > 0
+    monkeypatch.setenv("PLFX_FUSE", str(fuse))
+    c = plfx.Context(0)
+    try:
+        clv = [None if is_coded[t] else dev(dense[t]) for t in range(ntax)]
+        clv += [torch.zeros(16 * n, dtype=torch.float64, device="cuda") for _ in range(nslots - ntax)]
+        tips = [dev(codes[t]) if is_coded[t] else None for t in range(ntax)] + [None] * (nslots - ntax)
+        sums = torch.full((nops,), -7, dtype=torch.int64, device="cuda")
+        scal = [torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(nops)]
+        c.traverse(ops, clv, dev(pm), dev(EV), n, dev(wgt), scal, sums, tips=tips)
+        torch.cuda.synchronize()
+        sched = c.last_schedule()
+    finally:
+        c.close()
+    for s_ in range(ntax, nslots):
+        assert np.array_equal(bits(clv[s_].cpu().numpy()), bits(host[s_])), s_
+    assert np.array_equal(sums.cpu().numpy(), esums)
+    for j in range(nops):
+        assert np.array_equal(scal[j].cpu().numpy(), escal[j]), j
+    return sched
+
+
+# kernel launches of each case at PLFX_FUSE 3, 2 (measured before the planner
+# was split off plfx_traverse_tips: the issue order of the launches is part of
+# what graph captures replay)
+SCHEDULE_LAUNCHES = {("b16", "dense"): (1, 2), ("b64", "dense"): (1, 2), ("b64", "left"): (2, 2),
+                     ("b64", "mixed"): (4, 4), ("taxa53", "dense"): (8, 9), ("taxa53", "half"): (10, 10)}
+
+
+@pytest.mark.parametrize("fuse", [3, 2])
+@pytest.mark.parametrize("tree,mode", list(SCHEDULE_LAUNCHES))
+def test_schedule_is_the_planners(oracle, tree, mode, fuse, monkeypatch):
+    """What the library reports and runs is the planner's answer: the counts
+    tests/test_trav_plan.py pins on the CPU are last_schedule()'s on the GPU
+    (and the launch count is unchanged), with CLVs, scaler bytes and sums
+    bit-identical to the oracle."""
+    from test_trav_plan import PINNED
+
+    sched = _run_schedule_case(oracle, tree, mode, fuse, monkeypatch)
+    counts = next(row[2 + (3 - fuse)] for row in PINNED if row[0] == tree and mode in row[1])
+    keys = ("deep6", "deep5", "deep4", "septets", "triples", "unfused")
+    assert [sched[k] for k in keys] == counts, sched
+    assert sched["launches"] == SCHEDULE_LAUNCHES[(tree, mode)][3 - fuse], sched
 
 
 def _tree_driver_expected(oracle, taxa, n, seed, alpha=0.5):
