@@ -11,16 +11,17 @@
 // device code and its mapping are documented in plf_dna.hpp / DESIGN.md.
 //
 // Grids: grid-stride kernels launch at most the co-resident block count
-// (occupancy x CUs) times a tuned multiplier; batched launches spread those
-// blocks over the batch's nodes (blockIdx.y = node).
+// (occupancy x CUs, plf_launch.hpp grid_x); batched launches spread those
+// blocks over the batch's nodes (blockIdx.y = node).  Run-time choices (dtype,
+// scaler sum, tips, depth) become template arguments through dispatch().
 #include <hip/hip_runtime.h>
-
 
 #include <algorithm>
 #include <cstdint>
 
 #include "plf_dna.hpp"
 #include "plf_kernels.hpp"
+#include "plf_launch.hpp"
 #include "plf_lnl.hpp"
 #include "plf_pmat.hpp"
 #include "plf_prot.hpp"
@@ -30,6 +31,7 @@ namespace {
 
 using dev::kBlock;
 using dev::kWavesPerBlock;
+static_assert(kBlockThreads == kBlock, "block size mismatch");
 static_assert(kWsWords == dev::kWsWords, "workspace size mismatch");
 static_assert(kMaxBatch == dev::kMaxBatch, "batch size mismatch");
 static_assert(sizeof(NodeDescH) == sizeof(dev::NodeDesc), "node descriptor mismatch");
@@ -39,12 +41,12 @@ static_assert(sizeof(SeptetDescH) == sizeof(dev::SeptetDesc), "septet descriptor
 static_assert(kMaxSeptets == dev::kMaxSeptets, "septet batch size");
 static_assert(kDeepQueueRegion == dev::kDeepQueueRegion, "deep queue region");
 static_assert(sizeof(DeepDescH) == sizeof(dev::DeepDesc), "deep descriptor mismatch");
+static_assert(kProtCombos == dev::kProtCombos, "combination count");
 
 // Tuned on MI355X (tools/tune_plf.hip@f9b3af3, profiles/r01_tune.log):
 // f64 lane-pair kernel, 2 x 16-site steps per trip, non-temporal CLV loads
 // and stores, grid = resident blocks.
 constexpr int kU64 = 2, kU32 = 4;
-constexpr int kGridMul64 = 1, kGridMul32 = 1;
 constexpr bool kNt = true;   // f32: NT CLV loads (74.8% vs 70.2% of HBM peak, r01_tune_f32.log)
 constexpr bool kNtl64 = true;
 constexpr int kMinWaves = 1;
@@ -58,46 +60,6 @@ constexpr int kTripleU32 = 2;
 constexpr int kSeptetU = 2;
 constexpr int kSeptetU32 = 2;  // f32 (lane = category): 2 x 16-site blocks per trip
 constexpr int kDeepU32 = 2;    // f32 six-level pass: 2 x 16-site blocks per trip
-
-// Co-resident 256-thread blocks of `kernel` on the current device (cached per
-// kernel instantiation by the caller).
-int resident_blocks(const void *kernel, int &cache) {
-  if (!cache) {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    (void)hipGetDevice(&dev);
-    (void)hipGetDeviceProperties(&prop, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess ||
-        per_cu < 1)
-      per_cu = 2;
-    cache = per_cu * prop.multiProcessorCount;
-  }
-  return cache;
-}
-
-// blocks along x for `count` nodes of n sites each
-int64_t grid_x(const void *kernel, int &cache, int grid_mul, int64_t n, int sites_per_block,
-               int count, int max_blocks) {
-  int64_t blocks = (n + sites_per_block - 1) / sites_per_block;
-  const int64_t resident = (int64_t)grid_mul * resident_blocks(kernel, cache);
-  // floor: count x cap blocks must fit in one wave of resident blocks (a ceil
-  // would leave a few blocks for a second, nearly empty wave: +30% on a
-  // 10-node batch)
-  const int64_t cap = max_blocks > 0 ? max_blocks : std::max<int64_t>(1, resident / count);
-  if (blocks > cap) blocks = cap;
-  return blocks < 1 ? 1 : blocks;
-}
-
-int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus < 1) cus = 256;
-  }
-  return cus;
-}
 
 // Node kernels switch to the XCD-segmented site mapping (plf_dna.hpp
 // wave_sites, kSegL2 = 3) from min_sites up, or always / never with
@@ -130,15 +92,12 @@ hipError_t launch_cat(const DnaArgs &a, int max_blocks, hipStream_t s) {
   // on two streams at 256 blocks each run 0.773 of the HBM peak in 20-step
   // regions vs 0.746 at 512 (tools/probes/node_grid_lanes_f32.sh,
   // profiles/r06_probe_node_grid_lanes.log)
-  const int64_t gx = grid_x((const void *)kernel, cache, kGridMul32, a.n, kWavesPerBlock * 16 * kU32,
-                            1, max_blocks > 0 ? max_blocks
-                                              : std::max(1, kBlocksPerCu32 * cu_count() / std::max(1, a.streams)));
+  const int64_t gx = grid_x((const void *)kernel, cache, a.n, kWavesPerBlock * 16 * kU32, 1,
+                            max_blocks > 0 ? max_blocks
+                                           : std::max(1, kBlocksPerCu32 * cu_count() / std::max(1, a.streams)));
   const int64_t gs = segment_grid(a, gx, kSegMinSites32);
   if (gs) kernel = &dev::plf_dna_kernel<T, kU32, kSum, kNt, kMinWaves, 3>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(gs ? gs : gx)), dim3(kBlock), 0, s, (const T *)a.x1,
-                     (const T *)a.x2, (T *)a.x3, (const T *)a.EV, (const T *)a.left,
-                     (const T *)a.right, a.wgt, a.scaler, a.n, a.ws, a.scaler_sum);
-  return hipGetLastError();
+  return launch_node<T>(kernel, gs ? gs : gx, s, a);
 }
 
 template <bool kSum>
@@ -149,42 +108,29 @@ hipError_t launch_pair(const DnaArgs &a, int max_blocks, hipStream_t s) {
   // 512 blocks each (16 trips per block) run 0.775 in 20-step regions and 0.80
   // in 200-step ones, vs 0.750 / 0.778 at 1024 (8 trips); one node alone at
   // 512 runs 0.64 (tools/probes/node_grid_lanes.sh, profiles/r06_probe_node_grid_lanes.log)
-  const int64_t gx = grid_x((const void *)kernel, cache, kGridMul64, a.n, kWavesPerBlock * 16 * kU64,
+  const int64_t gx = grid_x((const void *)kernel, cache, a.n, kWavesPerBlock * 16 * kU64,
                             std::max(1, a.streams), max_blocks);
   const int64_t gs = segment_grid(a, gx, kSegMinSites64);
   if (gs) kernel = &dev::plf_dna_f64_pair_kernel<kU64, kSum, kMinWaves, kNtl64, 3>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(gs ? gs : gx)), dim3(kBlock), 0, s, (const double *)a.x1,
-                     (const double *)a.x2, (double *)a.x3, (const double *)a.EV,
-                     (const double *)a.left, (const double *)a.right, a.wgt, a.scaler, a.n, a.ws,
-                     a.scaler_sum);
-  return hipGetLastError();
+  return launch_node<double>(kernel, gs ? gs : gx, s, a);
 }
 
-template <bool kSum, int kTips>
-hipError_t launch_pair_batch(const dev::NodeBatch &b, int count, const double *EV,
-                             const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                             hipStream_t s, const double *tipvec, int share = 1) {
-  static int cache = 0;
-  auto kernel = &dev::plf_dna_f64_pair_batch_kernel<kU64, kSum, kMinWaves, kNtl64, kTips>;
-  // share: batches the caller keeps in flight on as many streams (plfx_ctx_set_streams)
-  const int64_t gx = grid_x((const void *)kernel, cache, kGridMul64, n, kWavesPerBlock * 16 * kU64,
-                            count * std::max(1, share), max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt, n,
-                     ws, tipvec);
-  return hipGetLastError();
-}
-
+// One template per batched launcher, f32 and f64: EV and tipvec are values of T.
 template <typename T, bool kSum, int kTips>
-hipError_t launch_cat_batch(const dev::NodeBatch &b, int count, const T *EV, const int32_t *wgt,
-                            int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s,
-                            const T *tipvec, int share = 1) {
+hipError_t launch_dna_batch_t(const dev::NodeBatch &b, int count, const void *EV, const int32_t *wgt,
+                              int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s,
+                              const void *tipvec, int share) {
   static int cache = 0;
-  auto kernel = &dev::plf_dna_batch_kernel<T, kU32, kSum, kNt, kMinWaves, kTips>;
-  const int64_t gx = grid_x((const void *)kernel, cache, kGridMul32, n, kWavesPerBlock * 16 * kU32,
+  auto kernel = [] {
+    if constexpr (sizeof(T) == 8) return &dev::plf_dna_f64_pair_batch_kernel<kU64, kSum, kMinWaves, kNtl64, kTips>;
+    else return &dev::plf_dna_batch_kernel<T, kU32, kSum, kNt, kMinWaves, kTips>;
+  }();
+  constexpr int U = sizeof(T) == 8 ? kU64 : kU32;
+  // share: batches the caller keeps in flight on as many streams (plfx_ctx_set_streams)
+  const int64_t gx = grid_x((const void *)kernel, cache, n, kWavesPerBlock * 16 * U,
                             count * std::max(1, share), max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt, n,
-                     ws, tipvec);
-  return hipGetLastError();
+  return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, b, (const T *)EV, wgt, n, ws,
+                (const T *)tipvec);
 }
 
 template <typename T, int S, int C>
@@ -195,18 +141,10 @@ hipError_t launch_lnl_t(const T *x, int64_t n, const double *catw, const double 
   auto kernel = &dev::root_lnl_kernel<T, S, C>;
   // C steps of 64/C sites per wave trip; 2 blocks per CU (more trips per wave: the
   // kernel is short and its ramp and final reduction weigh; tools/ab_lnl.hip@f9b3af3)
-  int64_t gx = grid_x((const void *)kernel, cache, 1, n, kWavesPerBlock * 64, 1, 0);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  }
-  if (cus > 0 && gx > 2 * (int64_t)cus) gx = 2 * (int64_t)cus;
-  if (gx > kLnlMaxGrid) gx = kLnlMaxGrid;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kBlock), 0, s, x, n, catw, freq, wgt, sums,
-                     nsums, partials, ticket, out, site_lnl);
-  return hipGetLastError();
+  int64_t gx = grid_x((const void *)kernel, cache, n, kWavesPerBlock * 64, 1, 0);
+  gx = std::min<int64_t>({gx, 2 * (int64_t)cu_count(), kLnlMaxGrid});
+  return launch(kernel, dim3((unsigned)gx), kBlock, s, x, n, catw, freq, wgt, sums, nsums, partials, ticket,
+                out, site_lnl);
 }
 
 // protein root lnL: 64-site LDS tiles, the co-resident grid (plf_lnl.hpp
@@ -217,23 +155,21 @@ hipError_t launch_lnl_prot_t(const T *x, int64_t n, const double *catw, const do
                              unsigned long long *ticket, double *out, double *site_lnl, hipStream_t s) {
   static int cache = 0;
   auto kernel = &dev::root_lnl_prot_kernel<T>;
-  int64_t gx = grid_x((const void *)kernel, cache, 1, n, 64, 1, 0);
-  if (gx > kLnlMaxGrid) gx = kLnlMaxGrid;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kBlock), 0, s, x, n, catw, freq, wgt, sums, nsums,
-                     partials, ticket, out, site_lnl);
-  return hipGetLastError();
+  const int64_t gx = std::min<int64_t>(grid_x((const void *)kernel, cache, n, 64, 1, 0), kLnlMaxGrid);
+  return launch(kernel, dim3((unsigned)gx), kBlock, s, x, n, catw, freq, wgt, sums, nsums, partials, ticket,
+                out, site_lnl);
 }
 
 template <typename T, bool kFma, bool kSum, int kTips>
-hipError_t launch_prot_t(const DnaArgs &a, int max_blocks, hipStream_t s, const T *tipvec) {
+hipError_t launch_prot_t(const DnaArgs &a, int max_blocks, hipStream_t s, const void *tipvec) {
   static_assert(sizeof(T) == 4, "f32 protein; f64 runs launch_prot_mfma_t / launch_prot_exact64_t");
+  static int cache = 0;
   // f32: FMA mode on the matrix cores (v_mfma_f32_16x16x4_f32 = fmaf chain;
   // rows 16..19 of the products and the back-transform on 4x4x1_16b, kQ = 2:
   // 52.4 -> 46.5 us at 2^18, profiles/r02_tune_protein_f32_q.log), exact mode
   // on the LDS-matrix kernel (4-row groups, tile prefetch)
   // (tools/tune_prot32.hip@f9b3af3, profiles/r02_tune_protein_f32.log)
   if constexpr (kFma) {
-    static int cache = 0;
     auto kernel = &dev::plf_prot_mfma32_kernel<kSum, 3, kTips>;
     // with `streams` calls in flight: the resident blocks per CU / streams,
     // rounded UP to whole blocks per CU (3 per CU -> 2 at two streams: 0.743-
@@ -241,27 +177,18 @@ hipError_t launch_prot_t(const DnaArgs &a, int max_blocks, hipStream_t s, const 
     // profiles/r06_probe_prot_grid_lanes.log)
     int cap = max_blocks;
     if (cap <= 0 && a.streams > 1) {
-      const int cus = cu_count(), per_cu = std::max(1, resident_blocks((const void *)kernel, cache) / cus);
+      const int cus = cu_count(), per_cu = std::max(1, resident_blocks((const void *)kernel, kBlock, 2, cache) / cus);
       cap = cus * ((per_cu + a.streams - 1) / a.streams);
     }
-    const int64_t gx = grid_x((const void *)kernel, cache, 1, a.n, 64, 1, cap);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kBlock), 0, s, (const T *)a.x1,
-                       (const T *)a.x2, (T *)a.x3, (const T *)a.EV, (const T *)a.left,
-                       (const T *)a.right, a.wgt, a.scaler, a.n, a.ws, a.scaler_sum, tipvec);
+    return launch_node<T>(kernel, grid_x((const void *)kernel, cache, a.n, 64, 1, cap), s, a, tipvec);
   } else {
-    static int cache = 0;
     auto kernel = &dev::plf_prot_lds_kernel<T, kSum, 2, kTips, 4, false>;
-    const int64_t gx = grid_x((const void *)kernel, cache, 1, a.n, 64, 1, max_blocks);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kBlock), 0, s, (const T *)a.x1,
-                       (const T *)a.x2, (T *)a.x3, (const T *)a.EV, (const T *)a.left,
-                       (const T *)a.right, a.wgt, a.scaler, a.n, a.ws, a.scaler_sum, tipvec);
+    return launch_node<T>(kernel, grid_x((const void *)kernel, cache, a.n, 64, 1, max_blocks), s, a, tipvec);
   }
-  return hipGetLastError();
 }
 
 template <bool kSum, int kTips>
-hipError_t launch_prot_mfma_t(const DnaArgs &a, int max_blocks, hipStream_t s,
-                              const double *tipvec) {
+hipError_t launch_prot_mfma_t(const DnaArgs &a, int max_blocks, hipStream_t s, const void *tipvec) {
   static int cache = 0;
   // X3 to LDS through permuted back-transform rows (kX3 = 2: conflict-free
   // b128 writes; 90.2 vs 91.2 us at 2^18, 342 vs 345 at 2^20, tools/tune_prot.hip@f9b3af3,
@@ -276,188 +203,124 @@ hipError_t launch_prot_mfma_t(const DnaArgs &a, int max_blocks, hipStream_t s,
   // +1-2 %; the VALU protein kernels keep their full grid, which measured best
   // with two in flight too -- tools/probes/prot_grid_lanes.sh,
   // profiles/r06_probe_prot_grid_lanes.log)
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, a.n, 64, std::max(1, a.streams), max_blocks);
-  auto launch = [&](auto k) {
-    hipLaunchKernelGGL(k, dim3((unsigned)gx), dim3(kBlock), 0, s, (const double *)a.x1,
-                       (const double *)a.x2, (double *)a.x3, (const double *)a.EV,
-                       (const double *)a.left, (const double *)a.right, a.wgt, a.scaler, a.n, a.ws,
-                       a.scaler_sum, tipvec);
-    return hipGetLastError();
-  };
+  const int64_t gx = grid_x((const void *)kernel, cache, a.n, 64, std::max(1, a.streams), max_blocks);
   if constexpr (kTips < 2)  // the queue form exists for dense and tip/inner nodes only
-    if (a.ws && (a.n + 63) / 64 >= 32 * gx) return launch(&dev::plf_prot_mfma_kernel<kSum, 2, kTips, true>);
-  return launch(kernel);
+    if (a.ws && (a.n + 63) / 64 >= 32 * gx) kernel = &dev::plf_prot_mfma_kernel<kSum, 2, kTips, true>;
+  return launch_node<double>(kernel, gx, s, a, tipvec);
 }
 
 template <bool kSum, int kTips>
-hipError_t launch_prot_exact64_t(const DnaArgs &a, int max_blocks, hipStream_t s,
-                                 const double *tipvec) {
+hipError_t launch_prot_exact64_t(const DnaArgs &a, int max_blocks, hipStream_t s, const void *tipvec) {
   static int cache = 0;
   // 10-row groups + tile prefetch (tools/tune_prot.hip@f9b3af3, profiles/r02_tune_protein_exact_rows.log)
   auto kernel = &dev::plf_prot_lds_kernel<double, kSum, 2, kTips, 10, true>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, a.n, 64, 1, max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kBlock), 0, s, (const double *)a.x1,
-                     (const double *)a.x2, (double *)a.x3, (const double *)a.EV,
-                     (const double *)a.left, (const double *)a.right, a.wgt, a.scaler, a.n, a.ws,
-                     a.scaler_sum, tipvec);
-  return hipGetLastError();
+  return launch_node<double>(kernel, grid_x((const void *)kernel, cache, a.n, 64, 1, max_blocks), s, a, tipvec);
 }
 
-// dtype x mode x scaler-sum x tips dispatch of the protein kernels
-template <int kTips>
-hipError_t launch_prot_tips(int dtype, bool fma, const DnaArgs &a, int max_blocks, hipStream_t s,
+template <typename T, bool kSum, int kTips>
+hipError_t launch_triples_t(const dev::TripleBatch &b, int count, const void *EV, const int32_t *wgt,
+                            int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s,
                             const void *tipvec) {
-  const bool sum = a.scaler_sum != nullptr;
-  const double *V64 = (const double *)tipvec;
-  const float *V32 = (const float *)tipvec;
-  if (dtype == 1) {
-    if (fma)  // matrix cores: bit-identical to the fused VALU chain (plf_prot.hpp)
-      return sum ? launch_prot_mfma_t<true, kTips>(a, max_blocks, s, V64)
-                 : launch_prot_mfma_t<false, kTips>(a, max_blocks, s, V64);
-    // exact: matrices broadcast from LDS (plf_prot.hpp)
-    return sum ? launch_prot_exact64_t<true, kTips>(a, max_blocks, s, V64)
-               : launch_prot_exact64_t<false, kTips>(a, max_blocks, s, V64);
-  }
-  if (fma)
-    return sum ? launch_prot_t<float, true, true, kTips>(a, max_blocks, s, V32)
-               : launch_prot_t<float, true, false, kTips>(a, max_blocks, s, V32);
-  return sum ? launch_prot_t<float, false, true, kTips>(a, max_blocks, s, V32)
-             : launch_prot_t<float, false, false, kTips>(a, max_blocks, s, V32);
+  static int cache = 0;
+  constexpr int U = sizeof(T) == 4 ? kTripleU32 : kTips ? kTripleUTips : kTripleU;
+  auto kernel = [] {
+    if constexpr (sizeof(T) == 8) return &dev::plf_dna_f64_triple_kernel<kSum, 1, kNtl64, kTips, U>;
+    else return &dev::plf_dna_cat_triple_kernel<T, kSum, 1, kNt, kTips, U>;
+  }();
+  const int64_t gx = grid_x((const void *)kernel, cache, n, kWavesPerBlock * 16 * U, count, max_blocks);
+  return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, b, (const T *)EV, wgt, n, ws,
+                (const T *)tipvec);
 }
 
-template <bool kSum, int kTips>
-hipError_t launch_triples_t(const dev::TripleBatch &b, int count, const double *EV,
-                            const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                            hipStream_t s, const double *tipvec) {
+template <typename T, bool kSum, int kTips>
+hipError_t launch_septets_t(const dev::SeptetBatch &b, int count, const void *EV, const int32_t *wgt,
+                            int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s,
+                            const void *tipvec) {
   static int cache = 0;
-  constexpr int U = kTips ? kTripleUTips : kTripleU;
-  auto kernel = &dev::plf_dna_f64_triple_kernel<kSum, 1, kNtl64, kTips, U>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, kWavesPerBlock * 16 * U, count,
-                            max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt,
-                     n, ws, tipvec);
-  return hipGetLastError();
-}
-
-template <bool kSum, int kTips>
-hipError_t launch_triples32_t(const dev::TripleBatch &b, int count, const float *EV,
-                              const int32_t *wgt, int64_t n, unsigned long long *ws,
-                              int max_blocks, hipStream_t s, const float *tipvec) {
-  static int cache = 0;
-  constexpr int U = kTripleU32;
-  auto kernel = &dev::plf_dna_cat_triple_kernel<float, kSum, 1, kNt, kTips, U>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, kWavesPerBlock * 16 * U, count,
-                            max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt,
-                     n, ws, tipvec);
-  return hipGetLastError();
-}
-
-template <bool kSum, int kTips>
-hipError_t launch_septets_t(const dev::SeptetBatch &b, int count, const double *EV,
-                            const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                            hipStream_t s, const double *tipvec) {
-  static int cache = 0;
-  // next-trip prefetch for dense leaves only: with coded leaves the pass is
-  // write-bound and the prefetch registers cost 4-4.5 % (r01_ab_fused_tips.log)
-  auto kernel = &dev::plf_dna_f64_septet_kernel<kSum, 1, kNtl64, kTips, kSeptetU, kTips == 0>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, kWavesPerBlock * 8 * kSeptetU, count,
-                            max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt,
-                     n, ws, tipvec);
-  return hipGetLastError();
-}
-
-template <bool kSum, int kTips>
-hipError_t launch_septets32_t(const dev::SeptetBatch &b, int count, const float *EV,
-                              const int32_t *wgt, int64_t n, unsigned long long *ws,
-                              int max_blocks, hipStream_t s, const float *tipvec) {
-  static int cache = 0;
-  auto kernel = &dev::plf_dna_cat_septet_kernel<float, kSum, 1, kNt, kTips, kSeptetU32>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, kWavesPerBlock * 16 * kSeptetU32,
-                            count, max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt,
-                     n, ws, tipvec);
-  return hipGetLastError();
+  auto kernel = [] {
+    // f64: next-trip prefetch for dense leaves only: with coded leaves the pass is
+    // write-bound and the prefetch registers cost 4-4.5 % (r01_ab_fused_tips.log)
+    if constexpr (sizeof(T) == 8) return &dev::plf_dna_f64_septet_kernel<kSum, 1, kNtl64, kTips, kSeptetU, kTips == 0>;
+    else return &dev::plf_dna_cat_septet_kernel<T, kSum, 1, kNt, kTips, kSeptetU32>;
+  }();
+  constexpr int kSites = sizeof(T) == 8 ? kWavesPerBlock * 8 * kSeptetU : kWavesPerBlock * 16 * kSeptetU32;
+  const int64_t gx = grid_x((const void *)kernel, cache, n, kSites, count, max_blocks);
+  return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, b, (const T *)EV, wgt, n, ws,
+                (const T *)tipvec);
 }
 
 // fused six-level subtrees: 512-thread blocks (one LDS copy of the 63 nodes'
 // matrices per 8 waves), 2 x 8-site blocks per trip, grid = co-resident blocks
 // (tools/gpu_deep.sh@f9b3af3, profiles/r01_deep.log)
-template <int D, typename T, bool kSum, int U, int kThreads, int kTips, bool kDyn>
-hipError_t launch_deep_k(const dev::DeepDesc &d, const T *EV, const int32_t *wgt, int64_t n,
-                         unsigned long long *ws, int max_blocks, hipStream_t s, const T *tipvec) {
-  static int resident = 0;
-  // f64: lane pairs, 8 sites per wave instruction; f32: lane = category, 16
-  auto kernel = [] {
-    if constexpr (sizeof(T) == 8) return &dev::plf_dna_f64_deep_kernel<D, kSum, kNtl64, U, kThreads, kTips, kDyn>;
-    else return &dev::plf_dna_cat_deep_kernel<D, T, kSum, kNt, U, kThreads, kTips, kDyn>;
-  }();
-  constexpr int kSitesPerWave = sizeof(T) == 8 ? 8 : 16;
-  if (!resident) {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    (void)hipGetDevice(&dev);
-    (void)hipGetDeviceProperties(&prop, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, kThreads, 0) !=
-            hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    resident = per_cu * prop.multiProcessorCount;
-  }
-  const int64_t per_block = (int64_t)(kThreads / 64) * kSitesPerWave * U;
-  int64_t gx = (n + per_block - 1) / per_block;
-  gx = std::max<int64_t>(1, std::min<int64_t>(gx, max_blocks > 0 ? max_blocks : resident));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(kThreads), 0, s, d, EV, wgt, n, ws, tipvec);
-  return hipGetLastError();
-}
-
-template <int D, typename T, bool kSum, int U, int kThreads, int kTips = 0>
-hipError_t launch_deep_t(const dev::DeepDesc &d, const T *EV, const int32_t *wgt, int64_t n,
-                         unsigned long long *ws, int max_blocks, hipStream_t s,
-                         const T *tipvec = nullptr) {
-  // chunks from the wave-level queue (plf_dna.hpp WaveQueue) whenever there is
+constexpr int kDeepThreads = 512;
+template <int D, typename T, bool kSum, int kTips>
+hipError_t launch_deep_t(const dev::DeepDesc &d, const void *EV, const int32_t *wgt, int64_t n,
+                         unsigned long long *ws, int max_blocks, hipStream_t s, const void *tipvec) {
+  // chunks from the wave-level queue (plf_dna.hpp WaveQueue, kDyn) whenever there is
   // a workspace: the fixed stride left wave exits spread over 2.61-3.36 ms of a
   // 2^20-site f64 pass (same process: 3358 -> 3116 us,
   // profiles/r03_tune_deep_dyn.log; bench tree64 f64 --tips 1688 -> 1643 us,
   // f32 --tips 875 -> 861, f32 dense equal, profiles/r03_ab_deep_dyn.log)
   // (the traversal always has a stream workspace when it launches a pass)
   if (!ws) return hipErrorInvalidValue;
-  return launch_deep_k<D, T, kSum, U, kThreads, kTips, true>(d, EV, wgt, n, ws, max_blocks, s, tipvec);
+  static int cache = 0;
+  // coded leaves, f32: 4 x 16-site blocks per trip, as f64: tree64 f32 --tips
+  // 0.664 (U = 2) -> 0.707 same box, U = 1 0.673; three-level passes 0.633
+  // (profiles/r03_ab_deep_tips_u_f32.log)
+  // coded leaves, f64: 4 x 8-site blocks per trip (every output stream gets 4 KiB
+  // runs per wave and trip; the pass is write-bound): 0.693 -> 0.727 of
+  // peak on tree64 --tips same box, U = 1 0.637; U = 6/8 spill
+  // (profiles/r03_ab_deep_tips_u.log)
+  constexpr int U = kTips == 2 ? 4 : sizeof(T) == 8 ? 2 : kDeepU32;
+  // f64: lane pairs, 8 sites per wave instruction; f32: lane = category, 16
+  auto kernel = [] {
+    if constexpr (sizeof(T) == 8) return &dev::plf_dna_f64_deep_kernel<D, kSum, kNtl64, U, kDeepThreads, kTips, true>;
+    else return &dev::plf_dna_cat_deep_kernel<D, T, kSum, kNt, U, kDeepThreads, kTips, true>;
+  }();
+  constexpr int kSitesPerWave = sizeof(T) == 8 ? 8 : 16;
+  const int64_t gx = grid_x((const void *)kernel, cache, n, (kDeepThreads / 64) * kSitesPerWave * U, 1,
+                            max_blocks, kDeepThreads, 1);
+  return launch(kernel, dim3((unsigned)gx), kDeepThreads, s, d, (const T *)EV, wgt, n, ws, (const T *)tipvec);
 }
+
+// Protein batches: grid (resident blocks, count) -- every node gets the grid a
+// one-node launch would (the kernels keep their one-node grid stride) and the
+// nodes' blocks follow each other through the co-resident slots.
+template <typename T, bool kFma, bool kSum, int kTips>
+hipError_t launch_prot_batch_t(const dev::NodeBatch &b, int count, const void *EV, const int32_t *wgt,
+                               int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s,
+                               const void *tipvec) {
+  static int cache = 0;
+  auto kernel = [] {
+    if constexpr (sizeof(T) == 8 && kFma) return &dev::plf_prot_mfma_batch_kernel<kSum, 2, kTips>;
+    else if constexpr (sizeof(T) == 8) return &dev::plf_prot_lds_batch_kernel<double, kSum, 2, kTips, 10, true>;
+    else if constexpr (kFma) return &dev::plf_prot_mfma32_batch_kernel<kSum, 3, kTips>;
+    else return &dev::plf_prot_lds_batch_kernel<float, kSum, 2, kTips, 4, false>;
+  }();
+  const int64_t gx = grid_x((const void *)kernel, cache, n, 64, 1, max_blocks);
+  return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, b, (const T *)EV, wgt, n, ws,
+                (const T *)tipvec);
+}
+
+template <typename T, bool kFma, bool kSum>
+hipError_t launch_prot_tab_t(const dev::ProtTabBatch &b, int count, const void *EV, const int32_t *wgt,
+                             int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s) {
+  static int cache = 0;
+  auto kernel = [] {
+    // exact: the exact bodies' shapes (launch_prot_t / launch_prot_exact64_t)
+    if constexpr (sizeof(T) == 8 && kFma) return &dev::plf_prot_mfma_tab_batch_kernel<kSum>;
+    else if constexpr (sizeof(T) == 8) return &dev::plf_prot_lds_tab_batch_kernel<double, kSum, 10, true>;
+    else if constexpr (kFma) return &dev::plf_prot_mfma32_tab_batch_kernel<kSum>;
+    else return &dev::plf_prot_lds_tab_batch_kernel<float, kSum, 4, false>;
+  }();
+  const int64_t gx = grid_x((const void *)kernel, cache, n, 64, 1, max_blocks);  // full grid per node
+  return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, b, (const T *)EV, wgt, n, ws);
+}
+
+using bools = among<false, true>;
+const auto node_sum = [](const auto &d) { return d.scaler_sum != nullptr; };
 
 }  // namespace
-
-template <int D>
-hipError_t launch_deep_d(int dtype, bool any_sum, const dev::DeepDesc &d, const void *EV,
-                         const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                         hipStream_t s, int tips, const void *tipvec) {
-  const double *E64 = (const double *)EV;
-  const float *E32 = (const float *)EV;
-  if (tips == 2 && dtype != 1) {  // coded leaves, f32
-    const float *V = (const float *)tipvec;
-    // 4 x 16-site blocks per trip, as f64: tree64 f32 --tips 0.664 (U = 2) ->
-    // 0.707 same box, U = 1 0.673; three-level passes 0.633
-    // (profiles/r03_ab_deep_tips_u_f32.log)
-    return any_sum ? launch_deep_t<D, float, true, 4, 512, 2>(d, E32, wgt, n, ws, max_blocks, s, V)
-                   : launch_deep_t<D, float, false, 4, 512, 2>(d, E32, wgt, n, ws, max_blocks, s, V);
-  }
-  if (tips == 2) {
-    const double *V = (const double *)tipvec;
-    // coded leaves: 4 x 8-site blocks per trip (every output stream gets 4 KiB
-    // runs per wave and trip; the pass is write-bound): 0.693 -> 0.727 of
-    // peak on tree64 --tips same box, U = 1 0.637; U = 6/8 spill
-    // (profiles/r03_ab_deep_tips_u.log)
-    return any_sum ? launch_deep_t<D, double, true, 4, 512, 2>(d, E64, wgt, n, ws, max_blocks, s, V)
-                   : launch_deep_t<D, double, false, 4, 512, 2>(d, E64, wgt, n, ws, max_blocks, s, V);
-  }
-  if (tips != 0) return hipErrorInvalidValue;
-  if (dtype == 1)
-    return any_sum ? launch_deep_t<D, double, true, 2, 512>(d, E64, wgt, n, ws, max_blocks, s)
-                   : launch_deep_t<D, double, false, 2, 512>(d, E64, wgt, n, ws, max_blocks, s);
-  return any_sum ? launch_deep_t<D, float, true, kDeepU32, 512>(d, E32, wgt, n, ws, max_blocks, s)
-                 : launch_deep_t<D, float, false, kDeepU32, 512>(d, E32, wgt, n, ws, max_blocks, s);
-}
 
 hipError_t launch_plf_dna_deep(int dtype, int depth, const DeepDescH *t, const void *EV,
                                const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
@@ -467,192 +330,82 @@ hipError_t launch_plf_dna_deep(int dtype, int depth, const DeepDescH *t, const v
   __builtin_memcpy(&d, t, sizeof(d));
   bool any_sum = false;
   for (int q = 0; q < (1 << depth) - 1; q++) any_sum |= t->ss[q] != nullptr;
-  switch (depth) {
-    case 4: return launch_deep_d<4>(dtype, any_sum, d, EV, wgt, n, ws, max_blocks, s, tips, tipvec);
-    case 5: return launch_deep_d<5>(dtype, any_sum, d, EV, wgt, n, ws, max_blocks, s, tips, tipvec);
-    default: return launch_deep_d<6>(dtype, any_sum, d, EV, wgt, n, ws, max_blocks, s, tips, tipvec);
-  }
+  // tips: every leaf dense (0) or every leaf coded (2)
+  return dispatch(
+      [&](auto kD, auto k64, auto kSum, auto kTips) {
+        return launch_deep_t<kD(), real_t<k64()>, kSum(), kTips()>(d, EV, wgt, n, ws, max_blocks, s, tipvec);
+      },
+      among<4, 5, 6>{depth}, bools{dtype == 1}, bools{any_sum}, among<0, 2>{tips});
 }
 
 hipError_t launch_plf_dna_septets(int dtype, const SeptetDescH *t, int count, const void *EV,
                                   const int32_t *wgt, int64_t n, unsigned long long *ws,
                                   int max_blocks, hipStream_t s, int tips, const void *tipvec) {
   if (count < 1 || count > kMaxSeptets || tips < 0 || tips > 2) return hipErrorInvalidValue;
-  dev::SeptetBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    __builtin_memcpy(&b.d[i], &t[i], sizeof(t[i]));
-    for (int q = 0; q < 7; q++) any_sum |= t[i].ss[q] != nullptr;
-  }
-  const double *E64 = (const double *)EV, *V64 = (const double *)tipvec;
-  const float *E32 = (const float *)EV, *V32 = (const float *)tipvec;
-  switch ((dtype == 1 ? 6 : 0) + (any_sum ? 3 : 0) + tips) {
-    case 0: return launch_septets32_t<false, 0>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 1: return launch_septets32_t<false, 1>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 2: return launch_septets32_t<false, 2>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 3: return launch_septets32_t<true, 0>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 4: return launch_septets32_t<true, 1>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 5: return launch_septets32_t<true, 2>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 6: return launch_septets_t<false, 0>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 7: return launch_septets_t<false, 1>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 8: return launch_septets_t<false, 2>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 9: return launch_septets_t<true, 0>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 10: return launch_septets_t<true, 1>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    default: return launch_septets_t<true, 2>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-  }
+  const auto p = pack<dev::SeptetBatch>(t, count, [](const SeptetDescH &d) {
+    return std::any_of(d.ss, d.ss + 7, [](const int64_t *ss) { return ss != nullptr; });
+  });
+  return dispatch(
+      [&](auto k64, auto kSum, auto kTips) {
+        return launch_septets_t<real_t<k64()>, kSum(), kTips()>(p.b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
+      },
+      bools{dtype == 1}, bools{p.any_sum}, among<0, 1, 2>{tips});
 }
 
 hipError_t launch_plf_dna_triples(int dtype, const TripleDescH *t, int count, const void *EV,
                                   const int32_t *wgt, int64_t n, unsigned long long *ws,
                                   int max_blocks, hipStream_t s, int tips, const void *tipvec) {
   if (count < 1 || count > kMaxTriples || tips < 0 || tips > 2) return hipErrorInvalidValue;
-  dev::TripleBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    static_assert(sizeof(b.d[0]) == sizeof(t[0]), "layout");
-    __builtin_memcpy(&b.d[i], &t[i], sizeof(t[i]));
-    any_sum |= t[i].ssa || t[i].ssb || t[i].ssp;
-  }
-  const double *E64 = (const double *)EV, *V64 = (const double *)tipvec;
-  const float *E32 = (const float *)EV, *V32 = (const float *)tipvec;
-  switch ((dtype == 1 ? 6 : 0) + (any_sum ? 3 : 0) + tips) {
-    case 0: return launch_triples32_t<false, 0>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 1: return launch_triples32_t<false, 1>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 2: return launch_triples32_t<false, 2>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 3: return launch_triples32_t<true, 0>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 4: return launch_triples32_t<true, 1>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 5: return launch_triples32_t<true, 2>(b, count, E32, wgt, n, ws, max_blocks, s, V32);
-    case 6: return launch_triples_t<false, 0>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 7: return launch_triples_t<false, 1>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 8: return launch_triples_t<false, 2>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 9: return launch_triples_t<true, 0>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    case 10: return launch_triples_t<true, 1>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-    default: return launch_triples_t<true, 2>(b, count, E64, wgt, n, ws, max_blocks, s, V64);
-  }
-}
-
-// Protein batches: grid (resident blocks, count) -- every node gets the grid a
-// one-node launch would (the kernels keep their one-node grid stride) and the
-// nodes' blocks follow each other through the co-resident slots.
-template <typename K, typename TT>
-hipError_t launch_prot_batch_k(K kernel, int &cache, const dev::NodeBatch &b, int count, const TT *EV,
-                               const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                               hipStream_t s, const TT *tipvec) {
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, 64, 1, max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, EV, wgt, n, ws,
-                     tipvec);
-  return hipGetLastError();
-}
-
-template <int kTips, bool kSum>
-hipError_t launch_prot_batch_t(int dtype, bool fma, const dev::NodeBatch &b, int count, const void *EV,
-                               const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
-                               hipStream_t s, const void *tipvec) {
-  const double *E64 = (const double *)EV, *V64 = (const double *)tipvec;
-  const float *E32 = (const float *)EV, *V32 = (const float *)tipvec;
-  if (dtype == 1 && fma) {
-    static int cache = 0;
-    return launch_prot_batch_k(&dev::plf_prot_mfma_batch_kernel<kSum, 2, kTips>, cache, b, count, E64, wgt,
-                               n, ws, max_blocks, s, V64);
-  }
-  if (dtype == 1) {
-    static int cache = 0;
-    return launch_prot_batch_k(&dev::plf_prot_lds_batch_kernel<double, kSum, 2, kTips, 10, true>, cache, b,
-                               count, E64, wgt, n, ws, max_blocks, s, V64);
-  }
-  if (fma) {
-    static int cache = 0;
-    return launch_prot_batch_k(&dev::plf_prot_mfma32_batch_kernel<kSum, 3, kTips>, cache, b, count, E32,
-                               wgt, n, ws, max_blocks, s, V32);
-  }
-  static int cache = 0;
-  return launch_prot_batch_k(&dev::plf_prot_lds_batch_kernel<float, kSum, 2, kTips, 4, false>, cache, b,
-                             count, E32, wgt, n, ws, max_blocks, s, V32);
+  const auto p = pack<dev::TripleBatch>(t, count, [](const TripleDescH &d) { return d.ssa || d.ssb || d.ssp; });
+  return dispatch(
+      [&](auto k64, auto kSum, auto kTips) {
+        return launch_triples_t<real_t<k64()>, kSum(), kTips()>(p.b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
+      },
+      bools{dtype == 1}, bools{p.any_sum}, among<0, 1, 2>{tips});
 }
 
 hipError_t launch_plf_prot_batch(int dtype, bool fma, const NodeDescH *nodes, int count, const void *EV,
                                  const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
                                  hipStream_t s, int tips, const void *tipvec) {
   if (count < 1 || count > kMaxBatch || tips < 0 || tips > 2) return hipErrorInvalidValue;
-  dev::NodeBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    b.d[i] = dev::NodeDesc{nodes[i].x1, nodes[i].x2, nodes[i].x3, nodes[i].left, nodes[i].right,
-                           nodes[i].scaler, nodes[i].scaler_sum};
-    any_sum |= nodes[i].scaler_sum != nullptr;
-  }
-  switch (tips * 2 + (any_sum ? 1 : 0)) {
-    case 0: return launch_prot_batch_t<0, false>(dtype, fma, b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
-    case 1: return launch_prot_batch_t<0, true>(dtype, fma, b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
-    case 2: return launch_prot_batch_t<1, false>(dtype, fma, b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
-    case 3: return launch_prot_batch_t<1, true>(dtype, fma, b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
-    case 4: return launch_prot_batch_t<2, false>(dtype, fma, b, count, EV, wgt, n, ws, max_blocks, s, tipvec);
-    // tips == 2 runs only as the combination tables of tip/tip nodes (plfx_api
-    // batch_impl), which carry no sum: a tip/tip node's sum comes from the
-    // gather, so the summing tip/tip forms are not built
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename T, bool kSum>
-hipError_t launch_gather_t(const dev::ProtGatherBatch &b, int count, const int32_t *wgt, int64_t n,
-                           unsigned long long *ws, int max_blocks, hipStream_t s) {
-  static int cache = 0;
-  auto kernel = &dev::prot_tiptip_gather_kernel<T, kSum>;
-  const int64_t gx = grid_x((const void *)kernel, cache, 1, n, 64, 1, max_blocks);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, wgt, n, ws);
-  return hipGetLastError();
+  const auto p = pack<dev::NodeBatch>(nodes, count, node_sum);
+  return dispatch(
+      [&](auto k64, auto kFma, auto kSum, auto kTips) {
+        // tips == 2 runs only as the combination tables of tip/tip nodes (plfx_api
+        // batch_impl), which carry no sum: a tip/tip node's sum comes from the
+        // gather, so the summing tip/tip forms are not built
+        if constexpr (kTips() == 2 && kSum()) return hipErrorInvalidValue;
+        else
+          return launch_prot_batch_t<real_t<k64()>, kFma(), kSum(), kTips()>(p.b, count, EV, wgt, n, ws,
+                                                                              max_blocks, s, tipvec);
+      },
+      bools{dtype == 1}, bools{fma}, bools{p.any_sum}, among<0, 1, 2>{tips});
 }
 
 hipError_t launch_prot_tiptip_gather(int dtype, const ProtGatherDescH *d, int count, const int32_t *wgt,
                                      int64_t n, unsigned long long *ws, int max_blocks, hipStream_t s) {
   if (count < 1 || count > kMaxBatch) return hipErrorInvalidValue;
-  static_assert(kProtCombos == dev::kProtCombos, "combination count");
-  dev::ProtGatherBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    static_assert(sizeof(b.d[0]) == sizeof(d[0]), "layout");
-    __builtin_memcpy(&b.d[i], &d[i], sizeof(d[i]));
-    any_sum |= d[i].scaler_sum != nullptr;
-  }
-  if (dtype == 1)
-    return any_sum ? launch_gather_t<double, true>(b, count, wgt, n, ws, max_blocks, s)
-                   : launch_gather_t<double, false>(b, count, wgt, n, ws, max_blocks, s);
-  return any_sum ? launch_gather_t<float, true>(b, count, wgt, n, ws, max_blocks, s)
-                 : launch_gather_t<float, false>(b, count, wgt, n, ws, max_blocks, s);
+  const auto p = pack<dev::ProtGatherBatch>(d, count, node_sum);
+  return dispatch(
+      [&](auto k64, auto kSum) {
+        static int cache = 0;
+        auto kernel = &dev::prot_tiptip_gather_kernel<real_t<k64()>, kSum()>;
+        const int64_t gx = grid_x((const void *)kernel, cache, n, 64, 1, max_blocks);
+        return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, p.b, wgt, n, ws);
+      },
+      bools{dtype == 1}, bools{p.any_sum});
 }
 
 hipError_t launch_prot_tab_batch(int dtype, bool fma, const ProtTabDescH *d, int count, const void *EV,
                                  const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
                                  hipStream_t s) {
   if (count < 1 || count > kMaxBatch) return hipErrorInvalidValue;
-  dev::ProtTabBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    static_assert(sizeof(b.d[0]) == sizeof(d[0]), "layout");
-    __builtin_memcpy(&b.d[i], &d[i], sizeof(d[i]));
-    any_sum |= d[i].scaler_sum != nullptr;
-  }
-  auto launch = [&](auto kernel, int &cache, auto ev) {
-    const int64_t gx = grid_x((const void *)kernel, cache, 1, n, 64, 1, max_blocks);  // full grid per node
-    hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)count), dim3(kBlock), 0, s, b, ev, wgt, n, ws);
-    return hipGetLastError();
-  };
-  static int c64 = 0, c64n = 0, c32 = 0, c32n = 0, x64 = 0, x64n = 0, x32 = 0, x32n = 0;
-  const double *E64 = static_cast<const double *>(EV);
-  const float *E32 = static_cast<const float *>(EV);
-  if (!fma) {  // the exact bodies' shapes (launch_prot_t / launch_prot_exact64_t)
-    if (dtype == 1)
-      return any_sum ? launch(&dev::plf_prot_lds_tab_batch_kernel<double, true, 10, true>, x64, E64)
-                     : launch(&dev::plf_prot_lds_tab_batch_kernel<double, false, 10, true>, x64n, E64);
-    return any_sum ? launch(&dev::plf_prot_lds_tab_batch_kernel<float, true, 4, false>, x32, E32)
-                   : launch(&dev::plf_prot_lds_tab_batch_kernel<float, false, 4, false>, x32n, E32);
-  }
-  if (dtype == 1)
-    return any_sum ? launch(&dev::plf_prot_mfma_tab_batch_kernel<true>, c64, E64)
-                   : launch(&dev::plf_prot_mfma_tab_batch_kernel<false>, c64n, E64);
-  return any_sum ? launch(&dev::plf_prot_mfma32_tab_batch_kernel<true>, c32, E32)
-                 : launch(&dev::plf_prot_mfma32_tab_batch_kernel<false>, c32n, E32);
+  const auto p = pack<dev::ProtTabBatch>(d, count, node_sum);
+  return dispatch(
+      [&](auto k64, auto kFma, auto kSum) {
+        return launch_prot_tab_t<real_t<k64()>, kFma(), kSum()>(p.b, count, EV, wgt, n, ws, max_blocks, s);
+      },
+      bools{dtype == 1}, bools{fma}, bools{p.any_sum});
 }
 
 hipError_t launch_plf_prot(int dtype, bool fma, const DnaArgs &a, int max_blocks, hipStream_t s,
@@ -660,20 +413,25 @@ hipError_t launch_plf_prot(int dtype, bool fma, const DnaArgs &a, int max_blocks
   // tip/tip nodes (tips == 2) always go through the combination tables of the
   // stream's workspace (launch_plf_prot_batch over the 576 code pairs, then
   // launch_prot_tiptip_gather), never a one-node kernel
-  switch (tips) {
-    case 0: return launch_prot_tips<0>(dtype, fma, a, max_blocks, s, tipvec);
-    case 1: return launch_prot_tips<1>(dtype, fma, a, max_blocks, s, tipvec);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch(
+      [&](auto k64, auto kFma, auto kSum, auto kTips) {
+        // f64 FMA on the matrix cores: bit-identical to the fused VALU chain;
+        // f64 exact: matrices broadcast from LDS (plf_prot.hpp)
+        if constexpr (k64() && kFma()) return launch_prot_mfma_t<kSum(), kTips()>(a, max_blocks, s, tipvec);
+        else if constexpr (k64()) return launch_prot_exact64_t<kSum(), kTips()>(a, max_blocks, s, tipvec);
+        else return launch_prot_t<float, kFma(), kSum(), kTips()>(a, max_blocks, s, tipvec);
+      },
+      bools{dtype == 1}, bools{fma}, bools{a.scaler_sum != nullptr}, among<0, 1>{tips});
 }
 
 hipError_t launch_plf_dna_f32(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  return a.scaler_sum ? launch_cat<float, true>(a, max_blocks, s)
-                      : launch_cat<float, false>(a, max_blocks, s);
+  return dispatch([&](auto kSum) { return launch_cat<float, kSum()>(a, max_blocks, s); },
+                  bools{a.scaler_sum != nullptr});
 }
 
 hipError_t launch_plf_dna_f64(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  return a.scaler_sum ? launch_pair<true>(a, max_blocks, s) : launch_pair<false>(a, max_blocks, s);
+  return dispatch([&](auto kSum) { return launch_pair<kSum()>(a, max_blocks, s); },
+                  bools{a.scaler_sum != nullptr});
 }
 
 hipError_t launch_plf_dna_batch(int dtype, const NodeDescH *nodes, int count, const void *EV,
@@ -681,51 +439,30 @@ hipError_t launch_plf_dna_batch(int dtype, const NodeDescH *nodes, int count, co
                                 int max_blocks, hipStream_t s, int tips, const void *tipvec,
                                 int share) {
   if (count < 1 || count > kMaxBatch || tips < 0 || tips > 2) return hipErrorInvalidValue;
-  dev::NodeBatch b{};
-  bool any_sum = false;
-  for (int i = 0; i < count; i++) {
-    b.d[i] = dev::NodeDesc{nodes[i].x1, nodes[i].x2, nodes[i].x3, nodes[i].left, nodes[i].right,
-                           nodes[i].scaler, nodes[i].scaler_sum};
-    any_sum |= nodes[i].scaler_sum != nullptr;
-  }
-  const int key = (dtype == 1 ? 6 : 0) + (any_sum ? 3 : 0) + tips;
-  const double *E64 = (const double *)EV;
-  const float *E32 = (const float *)EV;
-  const double *TV64 = (const double *)tipvec;
-  const float *TV32 = (const float *)tipvec;
-  switch (key) {
-    case 0: return launch_cat_batch<float, false, 0>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 1: return launch_cat_batch<float, false, 1>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 2: return launch_cat_batch<float, false, 2>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 3: return launch_cat_batch<float, true, 0>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 4: return launch_cat_batch<float, true, 1>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 5: return launch_cat_batch<float, true, 2>(b, count, E32, wgt, n, ws, max_blocks, s, TV32, share);
-    case 6: return launch_pair_batch<false, 0>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-    case 7: return launch_pair_batch<false, 1>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-    case 8: return launch_pair_batch<false, 2>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-    case 9: return launch_pair_batch<true, 0>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-    case 10: return launch_pair_batch<true, 1>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-    default: return launch_pair_batch<true, 2>(b, count, E64, wgt, n, ws, max_blocks, s, TV64, share);
-  }
+  const auto p = pack<dev::NodeBatch>(nodes, count, node_sum);
+  return dispatch(
+      [&](auto k64, auto kSum, auto kTips) {
+        return launch_dna_batch_t<real_t<k64()>, kSum(), kTips()>(p.b, count, EV, wgt, n, ws, max_blocks, s,
+                                                                 tipvec, share);
+      },
+      bools{dtype == 1}, bools{p.any_sum}, among<0, 1, 2>{tips});
 }
 
 hipError_t launch_root_lnl(int dtype, int states, const void *x, int64_t n, const double *catw,
                            const double *freq, const int32_t *wgt, const int64_t *scaler_sums,
                            int nsums, double *partials, unsigned long long *ticket, double *out,
                            double *site_lnl, hipStream_t s) {
-  if (states == 4 && dtype == 1)
-    return launch_lnl_t<double, 4, 4>((const double *)x, n, catw, freq, wgt, scaler_sums, nsums,
-                                      partials, ticket, out, site_lnl, s);
-  if (states == 4 && dtype == 0)
-    return launch_lnl_t<float, 4, 4>((const float *)x, n, catw, freq, wgt, scaler_sums, nsums,
-                                     partials, ticket, out, site_lnl, s);
-  if (states == 20 && dtype == 1)
-    return launch_lnl_prot_t<double>((const double *)x, n, catw, freq, wgt, scaler_sums, nsums,
-                                     partials, ticket, out, site_lnl, s);
-  if (states == 20 && dtype == 0)
-    return launch_lnl_prot_t<float>((const float *)x, n, catw, freq, wgt, scaler_sums, nsums,
-                                    partials, ticket, out, site_lnl, s);
-  return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto kStates, auto kDtype) {
+        using T = real_t<kDtype() == 1>;
+        if constexpr (kStates() == 4)
+          return launch_lnl_t<T, 4, 4>((const T *)x, n, catw, freq, wgt, scaler_sums, nsums, partials, ticket,
+                                       out, site_lnl, s);
+        else
+          return launch_lnl_prot_t<T>((const T *)x, n, catw, freq, wgt, scaler_sums, nsums, partials, ticket,
+                                      out, site_lnl, s);
+      },
+      among<4, 20>{states}, among<0, 1>{dtype});
 }
 
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n, int64_t *out,
@@ -734,9 +471,7 @@ hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t 
   const int64_t cap = max_blocks > 0 ? max_blocks : 2048;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(dev::scaler_sum_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, scaler,
-                     wgt, n, ws, out);
-  return hipGetLastError();
+  return launch(dev::scaler_sum_kernel, dim3((unsigned)blocks), kBlock, s, scaler, wgt, n, ws, out);
 }
 
 hipError_t launch_pmatrix(int dtype, bool eigen_conv, const double *eigen, int S,
@@ -746,23 +481,13 @@ hipError_t launch_pmatrix(int dtype, bool eigen_conv, const double *eigen, int S
   int64_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  const dim3 g((unsigned)blocks), b(kBlock);
-  if (dtype == 1) {
-    if (eigen_conv)
-      hipLaunchKernelGGL((dev::pmatrix_kernel<double, true>), g, b, 0, s, eigen, S, rates, ncat,
-                         blen, nbranch, (double *)out);
-    else
-      hipLaunchKernelGGL((dev::pmatrix_kernel<double, false>), g, b, 0, s, eigen, S, rates, ncat,
-                         blen, nbranch, (double *)out);
-  } else {
-    if (eigen_conv)
-      hipLaunchKernelGGL((dev::pmatrix_kernel<float, true>), g, b, 0, s, eigen, S, rates, ncat,
-                         blen, nbranch, (float *)out);
-    else
-      hipLaunchKernelGGL((dev::pmatrix_kernel<float, false>), g, b, 0, s, eigen, S, rates, ncat,
-                         blen, nbranch, (float *)out);
-  }
-  return hipGetLastError();
+  return dispatch(
+      [&](auto k64, auto kConv) {
+        using T = real_t<k64()>;
+        return launch(&dev::pmatrix_kernel<T, kConv()>, dim3((unsigned)blocks), kBlock, s, eigen, S, rates, ncat,
+                      blen, nbranch, (T *)out);
+      },
+      bools{dtype == 1}, bools{eigen_conv});
 }
 
 }  // namespace plfx

@@ -21,7 +21,7 @@ struct DnaArgs {
                             // non-null (2 x kWsWords words, zero at rest)
   int64_t n;
   int segments = -1;        // node kernels' XCD-segmented site mapping: -1 by size, 0 off,
-                            // 1 on (plf_kernels.hip use_segments; PLFX_NODE_SEGMENTS)
+                            // 1 on (plf_kernels.hip segment_grid; PLFX_NODE_SEGMENTS)
   int streams = 1;          // one-node calls the caller keeps in flight (plfx_ctx_set_streams):
                             // the dense DNA node kernels and the protein FMA kernels
                             // take the co-resident blocks / streams
@@ -36,9 +36,9 @@ hipError_t launch_plf_dna_f64(const DnaArgs &a, int max_blocks, hipStream_t s);
 // Protein (S=20, C=4) kernel; fma selects fused multiply-add.
 hipError_t launch_plf_prot(int dtype, bool fma, const DnaArgs &a, int max_blocks, hipStream_t s,
                            int tips = 0, const void *tipvec = nullptr);
-// Protein f64 in FMA mode on the VALU with LDS-tiled matrices (plf_prot_valu.hip,
-// PLFX_FMA | PLFX_VALU): bit-identical to the matrix-core FMA kernel, dense
-// children, one node.
+// Protein f64 in FMA mode on the VALU (plf_prot_valu.hip, PLFX_FMA | PLFX_VALU):
+// P and EV as wave-uniform scalar operands, LDS holds only the staged child
+// tile; bit-identical to the matrix-core FMA kernel, dense children, one node.
 hipError_t launch_plf_prot_valu_f64(const DnaArgs &a, int max_blocks, hipStream_t s);
 // Protein f64 in exact mode with the matrices as scalar operands
 // (plf_prot_valu_exact.hip): bit-identical to the LDS-matrix exact kernel.

@@ -35,6 +35,7 @@
 #include <cstdint>
 
 #include "plf_kernels.hpp"
+#include "plf_launch.hpp"
 #include "plf_prot_valu.hpp"
 
 namespace plfx {
@@ -67,29 +68,17 @@ hipError_t launch_valu_t(const DnaArgs &a, int max_blocks, hipStream_t s) {
   // tile per column chunk (2 spilled) -2 % / -6 % (plf_prot_valu.hpp@d4b0f72;
   // profiles/r06_probe_valu_nopf.log)
   auto kernel = &dev::plf_prot_valu_fma_kernel<kSum, kValuRows, kValuCols, kValuMinW>;
-  static int resident = 0;
-  if (!resident) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, dev::kBlock, 0) !=
-            hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    resident = per_cu * std::max(cus, 1);
-  }
-  int64_t gx = (a.n + 63) / 64;  // one 64-site tile per block trip
-  gx = std::max<int64_t>(1, std::min<int64_t>(gx, max_blocks > 0 ? max_blocks : resident));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(dev::kBlock), 0, s, (const double *)a.x1,
-                     (const double *)a.x2, (double *)a.x3, (const double *)a.EV, (const double *)a.left,
-                     (const double *)a.right, a.wgt, a.scaler, a.n, a.ws, a.scaler_sum);
-  return hipGetLastError();
+  static int cache = 0;
+  // one 64-site tile per block trip, the co-resident grid
+  const int64_t gx = grid_x((const void *)kernel, cache, a.n, 64, 1, max_blocks, dev::kBlock, 1);
+  return launch_node<double>(kernel, gx, s, a);
 }
 
 }  // namespace
 
 hipError_t launch_plf_prot_valu_f64(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  return a.scaler_sum ? launch_valu_t<true>(a, max_blocks, s) : launch_valu_t<false>(a, max_blocks, s);
+  return dispatch([&](auto kSum) { return launch_valu_t<kSum()>(a, max_blocks, s); },
+                  among<false, true>{a.scaler_sum != nullptr});
 }
 
 }  // namespace plfx

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "plf_kernels.hpp"
+#include "plf_launch.hpp"
 #include "plf_prot_valu.hpp"
 
 namespace plfx {
@@ -37,41 +38,26 @@ plf_prot_valu_exact_kernel(const double *__restrict__ x1, const double *__restri
 
 namespace {
 
-template <bool kSum, int kRows, int kCols, int kMinW>
-hipError_t launch_k(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  auto kernel = &dev::plf_prot_valu_exact_kernel<kSum, kRows, kCols, kMinW>;
-  static int resident = 0;
-  if (!resident) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, dev::kBlock, 0) !=
-            hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    resident = per_cu * std::max(cus, 1);
-  }
-  int64_t gx = (a.n + 63) / 64;
-  gx = std::max<int64_t>(1, std::min<int64_t>(gx, max_blocks > 0 ? max_blocks : resident));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)gx), dim3(dev::kBlock), 0, s, (const double *)a.x1,
-                     (const double *)a.x2, (double *)a.x3, (const double *)a.EV, (const double *)a.left,
-                     (const double *)a.right, a.wgt, a.scaler, a.n, a.ws, a.scaler_sum);
-  return hipGetLastError();
-}
-
 // 4 rows per chain group, 2-column double-buffered scalar chunks, 3 waves per
 // SIMD: 130.0-130.5 us at 2^18 sites against the LDS-matrix kernel's 143.6-143.9
 // on the same box (profiles/r06_protein_exact_forms.log, form 3; five forms
 // A/B'd, plf_prot_valu_exact.hip@5ad7aa8)
+constexpr int kExactRows = 4, kExactCols = 2, kExactMinW = 3;
+
 template <bool kSum>
 hipError_t launch_t(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  return launch_k<kSum, 4, 2, 3>(a, max_blocks, s);
+  auto kernel = &dev::plf_prot_valu_exact_kernel<kSum, kExactRows, kExactCols, kExactMinW>;
+  static int cache = 0;
+  // one 64-site tile per block trip, the co-resident grid
+  const int64_t gx = grid_x((const void *)kernel, cache, a.n, 64, 1, max_blocks, dev::kBlock, 1);
+  return launch_node<double>(kernel, gx, s, a);
 }
 
 }  // namespace
 
 hipError_t launch_plf_prot_valu_exact_f64(const DnaArgs &a, int max_blocks, hipStream_t s) {
-  return a.scaler_sum ? launch_t<true>(a, max_blocks, s) : launch_t<false>(a, max_blocks, s);
+  return dispatch([&](auto kSum) { return launch_t<kSum()>(a, max_blocks, s); },
+                  among<false, true>{a.scaler_sum != nullptr});
 }
 
 }  // namespace plfx

@@ -63,7 +63,7 @@ struct plfx_ctx {
   hipStream_t stream = nullptr;
   int max_blocks = 0;               // grid cap for the grid-stride kernels (0 = resident blocks)
   int node_segments = -1;           // node kernels' XCD-segmented mapping: -1 by size, 0 off, 1 on
-                                    // (PLFX_NODE_SEGMENTS; plf_kernels.hip use_segments)
+                                    // (PLFX_NODE_SEGMENTS; plf_kernels.hip segment_grid)
   int streams = 1;                  // one-node calls kept in flight (plfx_ctx_set_streams, PLFX_STREAMS)
   int fuse = 3;  // traverse: 3 six-level subtrees before 2's, 2 three-level subtrees +
                  // level pairs, 1 level pairs, 0 none (PLFX_FUSE)
@@ -135,11 +135,16 @@ int hip_fail(plfx_ctx *ctx, hipError_t e, const char *what) {
     if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
   } while (0)
 
+int check_dtype(plfx_ctx *ctx, int dtype) {
+  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  return PLFX_OK;
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // NULL is the HIP null stream, as in every HIP API; pass plfx_ctx_stream(ctx)
 // to run on the context's own stream.
-hipStream_t pick(plfx_ctx *, void *stream) { return reinterpret_cast<hipStream_t>(stream); }
+hipStream_t pick(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
 
 constexpr size_t kWsEntryBytes = kWsBytes + kLnlPartialBytes + kLnlTicketBytes;
 
@@ -335,22 +340,27 @@ int check_dev_args(plfx_ctx *ctx, const void *x1, const void *x2, const void *x3
   return PLFX_OK;
 }
 
-template <typename T>
-int plf_dev(plfx_ctx *ctx, const T *x1, const T *x2, T *x3, const T *EV, int64_t n, const T *left,
-            const T *right, const int32_t *wgt, uint8_t *scaler, int64_t *scaler_sum,
-            void *stream) {
-  int rc = check_dev_args(ctx, x1, x2, x3, EV, n, left, right, (size_t)n * 16 * sizeof(T));
+// n == 0: nothing is launched; the count scaler sums at sums (may be NULL) are
+// zero -- 8 zero bytes each, so root_lnl's f64 result goes through here too
+int zero_sums(plfx_ctx *ctx, hipStream_t s, void *sums, int count) {
+  if (sums && count > 0) PLFX_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)count * sizeof(int64_t), s));
+  return PLFX_OK;
+}
+
+// one DNA node of dtype (PLFX_F32 / PLFX_F64, checked by the caller)
+int plf_dev(plfx_ctx *ctx, int dtype, const void *x1, const void *x2, void *x3, const void *EV, int64_t n,
+            const void *left, const void *right, const int32_t *wgt, uint8_t *scaler,
+            int64_t *scaler_sum, void *stream) {
+  int rc = check_dev_args(ctx, x1, x2, x3, EV, n, left, right,
+                          (size_t)n * 16 * (dtype == PLFX_F32 ? 4 : 8));
   if (rc != PLFX_OK) return rc;
-  hipStream_t s = pick(ctx, stream);
-  if (n == 0) {
-    if (scaler_sum) PLFX_HIP(ctx, hipMemsetAsync(scaler_sum, 0, sizeof(int64_t), s));
-    return PLFX_OK;
-  }
+  hipStream_t s = pick(stream);
+  if (n == 0) return zero_sums(ctx, s, scaler_sum, 1);
   PLFX_WS(ctx, s, w);
   plfx::DnaArgs a{x1, x2, x3, EV, left, right, wgt, scaler, scaler_sum, w->ws, n, ctx->node_segments};
   a.streams = ctx->streams;
-  hipError_t e = sizeof(T) == 4 ? plfx::launch_plf_dna_f32(a, ctx->max_blocks, s)
-                                : plfx::launch_plf_dna_f64(a, ctx->max_blocks, s);
+  hipError_t e = dtype == PLFX_F32 ? plfx::launch_plf_dna_f32(a, ctx->max_blocks, s)
+                                   : plfx::launch_plf_dna_f64(a, ctx->max_blocks, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "plf_dna launch");
   return PLFX_OK;
 }
@@ -425,11 +435,10 @@ int plf_host(plfx_ctx *ctx, const T *x1, const T *x2, T *x3, const T *EV, int n,
       if (wgt)
         PLFX_HIP(ctx, hipMemcpyAsync(d + o_wgt + lo * 4, wgt + lo, (size_t)m * 4, hipMemcpyHostToDevice, s));
     }
-    rc = plf_dev<T>(ctx, reinterpret_cast<const T *>(d + o_x1 + off),
-                    reinterpret_cast<const T *>(d + o_x2 + off), reinterpret_cast<T *>(d + o_x3 + off),
-                    dm, std::max<int64_t>(m, 0), dm + 16, dm + 80,
-                    wgt ? reinterpret_cast<const int32_t *>(d + o_wgt + lo * 4) : nullptr, nullptr,
-                    dsum + used, s);
+    rc = plf_dev(ctx, sizeof(T) == 4 ? PLFX_F32 : PLFX_F64, d + o_x1 + off, d + o_x2 + off, d + o_x3 + off,
+                 dm, std::max<int64_t>(m, 0), dm + 16, dm + 80,
+                 wgt ? reinterpret_cast<const int32_t *>(d + o_wgt + lo * 4) : nullptr, nullptr,
+                 dsum + used, s);
     if (rc != PLFX_OK) return rc;
     if (m > 0) {
       PLFX_HIP(ctx, hipEventRecord(ctx->chunk_done[used], s));
@@ -465,12 +474,6 @@ int check_node(plfx_ctx *ctx, const plfx_node &d, int tips, int64_t n, int i, si
 
 size_t clv_bytes_of(int dtype, int states, int64_t n) {
   return (size_t)(n > 0 ? n : 0) * 4 * states * (dtype == PLFX_F32 ? 4 : 8);
-}
-
-// n == 0: nothing is launched; the count scaler sums at sums (may be NULL) are zero
-int zero_sums(plfx_ctx *ctx, hipStream_t s, int64_t *sums, int count) {
-  if (sums && count > 0) PLFX_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)count * sizeof(int64_t), s));
-  return PLFX_OK;
 }
 
 // The arrays of a traversal call (plfx_traverse_tips): its ops as node descriptors.
@@ -816,7 +819,7 @@ int plfx_ctx_synchronize(plfx_ctx *ctx) {
 
 int plfx_ctx_release_stream(plfx_ctx *ctx, void *stream) {
   PLFX_BIND(ctx);
-  hipStream_t s = pick(ctx, stream);
+  hipStream_t s = pick(stream);
   StreamWs *w = ws_find(ctx, s);
   if (!w) return PLFX_OK;  // no workspace held: nothing to release
   if (capturing(s))  // a wait on a capturing stream would invalidate the capture
@@ -865,14 +868,14 @@ int plfx_plf_dev_f32(plfx_ctx *ctx, const float *x1, const float *x2, float *x3,
                      int64_t n, const float *left, const float *right, const int32_t *wgt,
                      uint8_t *scaler, int64_t *scaler_sum, void *stream) {
   PLFX_BIND(ctx);
-  return plf_dev<float>(ctx, x1, x2, x3, EV, n, left, right, wgt, scaler, scaler_sum, stream);
+  return plf_dev(ctx, PLFX_F32, x1, x2, x3, EV, n, left, right, wgt, scaler, scaler_sum, stream);
 }
 
 int plfx_plf_dev_f64(plfx_ctx *ctx, const double *x1, const double *x2, double *x3,
                      const double *EV, int64_t n, const double *left, const double *right,
                      const int32_t *wgt, uint8_t *scaler, int64_t *scaler_sum, void *stream) {
   PLFX_BIND(ctx);
-  return plf_dev<double>(ctx, x1, x2, x3, EV, n, left, right, wgt, scaler, scaler_sum, stream);
+  return plf_dev(ctx, PLFX_F64, x1, x2, x3, EV, n, left, right, wgt, scaler, scaler_sum, stream);
 }
 
 int plfx_plf_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const void *x1,
@@ -880,29 +883,18 @@ int plfx_plf_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const void
                      const void *right, const int32_t *wgt, uint8_t *scaler,
                      int64_t *scaler_sum, void *stream) {
   PLFX_BIND(ctx);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (flags & ~(PLFX_FMA | PLFX_VALU)) return fail(ctx, PLFX_ERR_INVALID, "bad flags %d", flags);
   const bool valu = (flags & PLFX_VALU) != 0;
   if (valu && (states != 20 || dtype != PLFX_F64))
     return fail(ctx, PLFX_ERR_INVALID, "PLFX_VALU: protein (states 20), f64 only");
-  if (states == 4) {
-    return dtype == PLFX_F32
-               ? plf_dev<float>(ctx, (const float *)x1, (const float *)x2, (float *)x3,
-                                (const float *)EV, n, (const float *)left, (const float *)right,
-                                wgt, scaler, scaler_sum, stream)
-               : plf_dev<double>(ctx, (const double *)x1, (const double *)x2, (double *)x3,
-                                 (const double *)EV, n, (const double *)left,
-                                 (const double *)right, wgt, scaler, scaler_sum, stream);
-  }
+  if (states == 4) return plf_dev(ctx, dtype, x1, x2, x3, EV, n, left, right, wgt, scaler, scaler_sum, stream);
   if (states != 20) return fail(ctx, PLFX_ERR_UNSUPPORTED, "states=%d not built (4, 20)", states);
   int rc = check_dev_args(ctx, x1, x2, x3, EV, n, left, right,
                           (size_t)n * 80 * (dtype == PLFX_F32 ? 4 : 8));
   if (rc != PLFX_OK) return rc;
-  hipStream_t s = pick(ctx, stream);
-  if (n == 0) {
-    if (scaler_sum) PLFX_HIP(ctx, hipMemsetAsync(scaler_sum, 0, sizeof(int64_t), s));
-    return PLFX_OK;
-  }
+  hipStream_t s = pick(stream);
+  if (n == 0) return zero_sums(ctx, s, scaler_sum, 1);
   PLFX_WS(ctx, s, w);
   plfx::DnaArgs a{x1, x2, x3, EV, left, right, wgt, scaler, scaler_sum, w->ws, n};
   a.streams = ctx->streams;
@@ -922,7 +914,7 @@ int plfx_instance_run(plfx_ctx *ctx, const void *in_left, const void *in_right, 
   PLFX_BIND(ctx);
   if (layout != PLFX_LAYOUT_COMBINED && layout != PLFX_LAYOUT_SEPARATE)
     return fail(ctx, PLFX_ERR_INVALID, "bad layout %d", layout);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (window_size % 16 != 0) return fail(ctx, PLFX_ERR_INVALID, "window_size %u not a multiple of 16", window_size);
   if (!in_left || !in_right) return fail(ctx, PLFX_ERR_INVALID, "null instance buffer");
   // Header words: in_left = [EV | P_L] (mm2sleft reads mem[0], mem[1..4]);
@@ -936,13 +928,8 @@ int plfx_instance_run(plfx_ctx *ctx, const void *in_left, const void *in_right, 
   const void *x1 = L + 80 * es;
   const void *right = R + (rhdr - 64) * es;
   const void *x2 = R + rhdr * es;
-  if (dtype == PLFX_F32)
-    return plf_dev<float>(ctx, (const float *)x1, (const float *)x2, (float *)out_clv,
-                          (const float *)EV, alignment_sites, (const float *)left,
-                          (const float *)right, nullptr, out_scaler, nullptr, stream);
-  return plf_dev<double>(ctx, (const double *)x1, (const double *)x2, (double *)out_clv,
-                         (const double *)EV, alignment_sites, (const double *)left,
-                         (const double *)right, nullptr, out_scaler, nullptr, stream);
+  return plf_dev(ctx, dtype, x1, x2, out_clv, EV, alignment_sites, left, right, nullptr, out_scaler, nullptr,
+                 stream);
 }
 
 int plfx_instance_run_host(plfx_ctx *ctx, const void *in_left, const void *in_right,
@@ -951,7 +938,7 @@ int plfx_instance_run_host(plfx_ctx *ctx, const void *in_left, const void *in_ri
   PLFX_BIND(ctx);
   if (layout != PLFX_LAYOUT_COMBINED && layout != PLFX_LAYOUT_SEPARATE)
     return fail(ctx, PLFX_ERR_INVALID, "bad layout %d", layout);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (!in_left || !in_right || (alignment_sites > 0 && !out_clv))
     return fail(ctx, PLFX_ERR_INVALID, "null instance buffer");
   const size_t es = dtype == PLFX_F32 ? 4 : 8, n = alignment_sites;
@@ -980,12 +967,12 @@ int plfx_instance_run_host(plfx_ctx *ctx, const void *in_left, const void *in_ri
 int plfx_plf_batch_dev(plfx_ctx *ctx, int dtype, int states, const plfx_node *nodes, int count,
                        const void *EV, int64_t n, const int32_t *wgt, void *stream) {
   PLFX_BIND(ctx);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (states != 4 && states != 20)
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "batched nodes: states=%d not built (4, 20)", states);
   // DNA batches share the resident grid with the batches of the other
   // streams in flight (plfx_ctx_set_streams)
-  return batch_impl(ctx, dtype, nodes, count, EV, n, wgt, pick(ctx, stream), 0, nullptr, states,
+  return batch_impl(ctx, dtype, nodes, count, EV, n, wgt, pick(stream), 0, nullptr, states,
                     PLFX_EXACT, nullptr, nullptr, nullptr, ctx->streams);
 }
 
@@ -995,7 +982,7 @@ int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const
                           const int32_t *wgt, uint8_t *scaler, int64_t *scaler_sum,
                           const void *tipvec, void *stream) {
   PLFX_BIND(ctx);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (states != 4 && states != 20)
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "states=%d not built (4, 20)", states);
   if (flags & ~PLFX_FMA) return fail(ctx, PLFX_ERR_INVALID, "bad flags %d", flags);
@@ -1008,7 +995,7 @@ int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const
     std::swap(nd.x1, nd.x2);
     std::swap(nd.left, nd.right);
   }
-  return batch_impl(ctx, dtype, &nd, 1, EV, n, wgt, pick(ctx, stream), tips, tipvec, states, flags);
+  return batch_impl(ctx, dtype, &nd, 1, EV, n, wgt, pick(stream), tips, tipvec, states, flags);
 }
 
 int plfx_plf_tips_dev(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1,
@@ -1037,7 +1024,7 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   for (int &c : ctx->sched) c = 0;
   if (states != 4 && states != 20)
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "traverse: states=%d not built (4, 20)", states);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (flags & ~PLFX_FMA) return fail(ctx, PLFX_ERR_INVALID, "bad flags %d", flags);
   if (nops < 0 || (nops > 0 && (!ops || !clv || !pmats || !EV)))
     return fail(ctx, PLFX_ERR_INVALID, "bad traverse arguments");
@@ -1053,7 +1040,7 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
     return fail(ctx, PLFX_ERR_INVALID, "%s", plan_err.c_str());
   int sched[PLFX_SCHED_COUNTS] = {};  // as plfx_traverse_schedule reports it; [6]: launches
   std::copy(plan.counts, plan.counts + 6, sched);
-  hipStream_t s = pick(ctx, stream);
+  hipStream_t s = pick(stream);
   if (n == 0) {  // nothing to launch
     const int rc = zero_sums(ctx, s, scaler_sums, nops);
     if (rc != PLFX_OK) return rc;
@@ -1202,14 +1189,14 @@ int plfx_root_lnl(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n
                   const int64_t *scaler_sums, int nsums, double *out_lnl, double *site_lnl,
                   void *stream) {
   PLFX_BIND(ctx);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (states != 4 && states != 20) return fail(ctx, PLFX_ERR_UNSUPPORTED, "lnl: states=%d", states);
   if (!out_lnl || n < 0 || (n > 0 && !x) || nsums < 0 || (nsums > 0 && !scaler_sums))
     return fail(ctx, PLFX_ERR_INVALID, "bad root_lnl arguments");
-  hipStream_t s = pick(ctx, stream);
+  hipStream_t s = pick(stream);
   if (n == 0) {
-    PLFX_HIP(ctx, hipMemsetAsync(out_lnl, 0, sizeof(double), s));
-    if (nsums == 0) return PLFX_OK;
+    const int rc = zero_sums(ctx, s, out_lnl, 1);
+    if (rc != PLFX_OK || nsums == 0) return rc;
   }
   PLFX_WS(ctx, s, w);
   hipError_t e = plfx::launch_root_lnl(dtype, states, x, n, catw, freq, wgt, scaler_sums, nsums,
@@ -1222,11 +1209,8 @@ int plfx_scaler_sum(plfx_ctx *ctx, const uint8_t *scaler, const int32_t *wgt, in
                     int64_t *out_sum, void *stream) {
   PLFX_BIND(ctx);
   if (!out_sum || n < 0 || (n > 0 && !scaler)) return fail(ctx, PLFX_ERR_INVALID, "bad scaler_sum args");
-  hipStream_t s = pick(ctx, stream);
-  if (n == 0) {
-    PLFX_HIP(ctx, hipMemsetAsync(out_sum, 0, sizeof(int64_t), s));
-    return PLFX_OK;
-  }
+  hipStream_t s = pick(stream);
+  if (n == 0) return zero_sums(ctx, s, out_sum, 1);
   PLFX_WS(ctx, s, w);
   hipError_t e = plfx::launch_scaler_sum(scaler, wgt, n, out_sum, w->ws, ctx->max_blocks, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "scaler_sum launch");
@@ -1237,7 +1221,7 @@ int plfx_pmatrix(plfx_ctx *ctx, int dtype, int states, int convention, const dou
                  const double *rates, int ncat, const double *blen, int64_t nbranch, void *pmats,
                  void *stream) {
   PLFX_BIND(ctx);
-  if (dtype != PLFX_F32 && dtype != PLFX_F64) return fail(ctx, PLFX_ERR_INVALID, "bad dtype %d", dtype);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (convention != PLFX_PMAT_STATE && convention != PLFX_PMAT_EIGEN)
     return fail(ctx, PLFX_ERR_INVALID, "bad convention %d", convention);
   if (states < 2 || states > 64 || ncat < 1 || nbranch < 0)
@@ -1245,7 +1229,7 @@ int plfx_pmatrix(plfx_ctx *ctx, int dtype, int states, int convention, const dou
   if (nbranch == 0) return PLFX_OK;
   if (!eigen || !rates || !blen || !pmats) return fail(ctx, PLFX_ERR_INVALID, "null pmatrix pointer");
   hipError_t e = plfx::launch_pmatrix(dtype, convention == PLFX_PMAT_EIGEN, eigen, states, rates,
-                                      ncat, blen, nbranch, pmats, pick(ctx, stream));
+                                      ncat, blen, nbranch, pmats, pick(stream));
   if (e != hipSuccess) return hip_fail(ctx, e, "pmatrix launch");
   return PLFX_OK;
 }

@@ -220,6 +220,19 @@ def test_every_stamped_kernel_resolves():
     assert seen > 0
 
 
+def test_kernel_instantiations_are_the_pinned_set():
+    """The kernels the library holds (mangled names of the functions with a
+    kernel descriptor, over its gfx950 code objects) are exactly those listed
+    in tests/golden/kernel_symbols.txt: a new or lost template instantiation
+    is a deliberate edit of that file."""
+    from plfx import codeobj
+
+    syms = codeobj._all_symbols(codeobj.default_lib())
+    have = {nm for nm, (_, typ, _, size) in syms.items() if typ == 2 and size > 0 and nm + ".kd" in syms}
+    pinned = set((ROOT / "tests" / "golden" / "kernel_symbols.txt").read_text().split())
+    assert have == pinned, f"added: {sorted(have - pinned)}\nremoved: {sorted(pinned - have)}"
+
+
 def test_launch_check_against_record_shapes():
     """a PMC record counts only for the dispatch it measured --
     the timed graph's kernel nodes (mangled names, grid and workgroup sizes)

@@ -6,6 +6,7 @@ within the north-star tolerance |a-b| <= 1e-10 * |b| (asserted separately)."""
 import hashlib
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -535,6 +536,168 @@ def test_streams_setting_grids_and_bits(oracle, monkeypatch, streams):
     assert c.streams == 1
     c.close()
     monkeypatch.delenv("PLFX_STREAMS")
+
+
+def _kernel_base(name):
+    """The identifier of a plfx::dev kernel from its mangled name
+    (_ZN4plfx3dev<len><identifier>...), template arguments dropped."""
+    m = re.match(r"_ZN4plfx3dev(\d+)", name or "")
+    return name[m.end():m.end() + int(m.group(1))] if m else name
+
+
+def test_launch_shapes_table(monkeypatch):
+    """Every launcher's (kernel, workgroups, workgroup size) at n = 4099 sites,
+    where the site count sets each grid (ceil(4099 / sites per block) is far
+    below the co-resident blocks), against the table below; then the grid cap
+    (PLFX_MAX_BLOCKS=3: 3 blocks per node, per batch entry, per deep pass) and
+    the f64 node's share with two streams in flight (half the grid).  Shapes
+    only: the values are checked by the parity tests; every context serves at
+    most PLFX_WS_POOL captures, since a captured stream keeps its workspace."""
+    import torch
+
+    import plfx
+
+    n = 4099
+    g = torch.Generator(device="cuda")
+    g.manual_seed(3)
+    f64, f32 = torch.float64, torch.float32
+
+    def rnd(count, dt):
+        return torch.rand(count, dtype=dt, device="cuda", generator=g)
+
+    def shapes(call):
+        return sorted((_kernel_base(nm), wgs, wg) for nm, wgs, wg in _captured_grids(call))
+
+    def node_args(dt, m, states=4):
+        V, S2 = 4 * states, states * states
+        return (rnd(V * m, dt), rnd(V * m, dt), torch.empty(V * m, dtype=dt, device="cuda"), rnd(S2, dt),
+                rnd(4 * S2, dt), rnd(4 * S2, dt))
+
+    def node(c, dt, m=n):
+        a = node_args(dt, m)
+        sc = torch.empty(m, dtype=torch.uint8, device="cuda")
+        s = torch.zeros(1, dtype=torch.int64, device="cuda")
+        return shapes(lambda sh: c.plf_dev(*a, None, sc, s, stream=sh))
+
+    def batch(c, dt, states=4):
+        a, b = node_args(dt, n, states), node_args(dt, n, states)
+        nodes = [dict(x1=t[0], x2=t[1], x3=t[2], left=t[4], right=t[5],
+                      scaler_sum=torch.zeros(1, dtype=torch.int64, device="cuda")) for t in (a, b)]
+        return shapes(lambda sh: c.plf_batch_dev(nodes, a[3], n, stream=sh, states=states))
+
+    def tree(c, dt, ntax, coded, states=4, fma=False):
+        """A balanced ntax-taxon tree, every leaf dense or every leaf coded."""
+        V, M = 4 * states, 4 * states * states
+        ops, level, slot = [], list(range(ntax)), ntax
+        while len(level) > 1:
+            nxt = []
+            for i in range(0, len(level), 2):
+                ops.append([slot, level[i], level[i + 1], len(ops)])
+                nxt.append(slot)
+                slot += 1
+            level = nxt
+        inner = [torch.empty(V * n, dtype=dt, device="cuda") for _ in range(slot - ntax)]
+        clv = [None if coded else rnd(V * n, dt) for _ in range(ntax)] + inner
+        tips = None
+        if coded:  # DNA state bits 1..15, protein code indices
+            tips = [torch.randint(1, 16, (n,), dtype=torch.uint8, device="cuda", generator=g)
+                    for _ in range(ntax)] + [None] * len(inner)
+        pm, EV = rnd(len(ops) * 2 * M, dt) * 0.3, rnd(states * states, dt)
+        sums = torch.zeros(len(ops), dtype=torch.int64, device="cuda")
+        return shapes(lambda sh: c.traverse(np.array(ops, np.int32), clv, pm, EV, n, None, None, sums,
+                                            stream=sh, tips=tips, states=states, fma=fma))
+
+    def fuse_ctx(level, **env):
+        for k, v in dict(env, PLFX_FUSE=level).items():
+            monkeypatch.setenv(k, v)
+        try:
+            return plfx.Context(0)
+        finally:
+            for k in dict(env, PLFX_FUSE=level):
+                monkeypatch.delenv(k)
+
+    got, want = {}, {}
+
+    def row(key, shapes_, expected):
+        got[key], want[key] = shapes_, sorted(expected)
+
+    # workgroups = ceil(4099 / sites per block): 64 -> 65, 128 -> 33, 256 -> 17, 512 -> 9
+    c = fuse_ctx("3")
+    try:
+        row("f64 node", node(c, f64), [("plf_dna_f64_pair_kernel", 33, 256)])
+        row("f32 node", node(c, f32), [("plf_dna_kernel", 17, 256)])
+        p64, p32 = node_args(f64, n, 20), node_args(f32, n, 20)
+        sc = torch.empty(n, dtype=torch.uint8, device="cuda")
+        s = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+        def protein_nodes(sh):
+            c.plf_dev_gen(*p64, 20, None, sc, s, stream=sh)  # f64 exact: scalar operands
+            c.plf_dev_gen(*p64, 20, None, sc, s, fma=True, stream=sh)  # matrix cores
+            c.plf_dev_gen(*p64, 20, None, sc, s, fma=True, valu=True, stream=sh)
+            c.plf_dev_gen(*p32, 20, None, sc, s, fma=True, stream=sh)
+            c.plf_dev_gen(*p32, 20, None, sc, s, stream=sh)  # f32 exact: LDS matrices
+            # the one-node launch behind the tip entry point: f64 exact on the LDS-matrix kernel
+            c.plf_tips_dev(p64[2], p64[3], n, p64[4], p64[5], x1=p64[0], x2=p64[1], scaler=sc,
+                           scaler_sum=s, stream=sh, states=20)
+
+        row("protein nodes", shapes(protein_nodes),
+            [(k, 65, 256) for k in ("plf_prot_valu_exact_kernel", "plf_prot_mfma_kernel",
+                                    "plf_prot_valu_fma_kernel", "plf_prot_mfma32_kernel",
+                                    "plf_prot_lds_kernel", "plf_prot_lds_kernel")])
+        row("protein batch", batch(c, f64, 20), [("plf_prot_lds_batch_kernel", 2 * 65, 256)])
+        # two tip/tip nodes (their 576 code pairs: 9 blocks each, then the
+        # gather), then their parent from the two tables
+        row("protein tip/tip tree", tree(c, f64, 4, True, states=20, fma=True),
+            [("plf_prot_mfma_batch_kernel", 2 * 9, 256), ("prot_tiptip_gather_kernel", 2 * 65, 256),
+             ("plf_prot_mfma_tab_batch_kernel", 65, 256)])
+        out = torch.zeros(1, dtype=f64, device="cuda")
+
+        def lnls(sh):
+            c.root_lnl(p64[0], n, out, stream=sh)
+            c.root_lnl(p64[0], n, out, states=20, stream=sh)
+
+        row("root lnL", shapes(lnls), [("root_lnl_kernel", 17, 256), ("root_lnl_prot_kernel", 65, 256)])
+    finally:
+        c.close()
+    c = fuse_ctx("3")  # 16 taxa: one depth-4 pass, 512-thread blocks
+    try:
+        row("f64 deep, dense", tree(c, f64, 16, False), [("plf_dna_f64_deep_kernel", 33, 512)])
+        row("f64 deep, tips", tree(c, f64, 16, True), [("plf_dna_f64_deep_kernel", 17, 512)])
+        row("f32 deep, dense", tree(c, f32, 16, False), [("plf_dna_cat_deep_kernel", 17, 512)])
+        row("f32 deep, tips", tree(c, f32, 16, True), [("plf_dna_cat_deep_kernel", 9, 512)])
+        # two streams in flight: the f64 node takes half the co-resident grid
+        one = node(c, f64, 1 << 20)
+        c.set_streams(2)
+        two = node(c, f64, 1 << 20)
+        assert len(one) == len(two) == 1 and two[0][1] * 2 == one[0][1], (one, two)
+        assert one[0][0] == two[0][0] == "plf_dna_f64_pair_kernel"
+    finally:
+        c.close()
+    c = fuse_ctx("2")  # 8 taxa: one three-level pass
+    try:
+        row("f64 three-level", tree(c, f64, 8, False), [("plf_dna_f64_septet_kernel", 65, 256)])
+        row("f32 three-level", tree(c, f32, 8, False), [("plf_dna_cat_septet_kernel", 33, 256)])
+        row("f64 batch", batch(c, f64), [("plf_dna_f64_pair_batch_kernel", 2 * 33, 256)])
+        row("f32 batch", batch(c, f32), [("plf_dna_batch_kernel", 2 * 17, 256)])
+    finally:
+        c.close()
+    c = fuse_ctx("1")  # 4 taxa: one level pair
+    try:
+        row("f64 level pair, dense", tree(c, f64, 4, False), [("plf_dna_f64_triple_kernel", 65, 256)])
+        row("f64 level pair, tips", tree(c, f64, 4, True), [("plf_dna_f64_triple_kernel", 33, 256)])
+        row("f32 level pair", tree(c, f32, 4, False), [("plf_dna_cat_triple_kernel", 33, 256)])
+    finally:
+        c.close()
+    c = fuse_ctx("3", PLFX_MAX_BLOCKS="3")
+    try:
+        row("capped node", node(c, f64), [("plf_dna_f64_pair_kernel", 3, 256)])
+        row("capped batch", batch(c, f64), [("plf_dna_f64_pair_batch_kernel", 2 * 3, 256)])
+        row("capped deep", tree(c, f64, 16, False), [("plf_dna_f64_deep_kernel", 3, 512)])
+    finally:
+        c.close()
+    for key in want:
+        print(key, got[key])
+    assert got == want, {k: (got[k], want[k]) for k in want if got[k] != want[k]}
 
 
 def test_plf_dev_repeated_calls_and_optional_outputs(ctx, oracle):
