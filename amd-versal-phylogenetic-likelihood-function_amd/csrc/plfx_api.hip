@@ -11,51 +11,28 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
-#include <deque>
 #include <new>
 #include <string>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/plfx.h"
 #include "plf_kernels.hpp"
+#include "stream_ws.hpp"
 #include "testbench.hpp"
 #include "trav_plan.hpp"
 
 constexpr int kHostChunksMax = 16;
 
-// Scaler-sum / lnL reduction workspace of one stream (plf_dna.hpp
-// block_ticket_sum, plf_lnl.hpp): zero at rest, restored to zero by the last
-// arriving block of every launch.  One per stream, so sum-producing launches
-// on different streams of one context may overlap (plfx.h, "Streams and the
-// scaler-sum workspace").  hipStreamPerThread is one handle value that names a
-// different stream in every host thread, so its workspaces are keyed by
-// (handle, thread).  Entries come from a pool allocated and zeroed with the
-// context (no allocation on a call path for the first kWsPool streams, so a
-// stream's first use may be inside a graph capture); plfx_ctx_release_stream
-// returns an entry to the pool -- unless a graph was captured through it: the
-// graph's replays keep using the entry's words, so it is retired (never handed
-// to another stream) and the context waits for the device when destroyed.
+// The per-stream reduction workspaces (stream_ws.hpp: who holds which entry
+// and when it may change hands) are allocated here: kWsPool entries with the
+// context, further ones stream-ordered on the stream that needs one.
 // plfx_ctx_destroy never touches a caller's stream handle (the stream may be
 // gone by then): an entry still held by a stream other than the context's is
 // waited for device-wide.  (An event recorded after each call cannot stand
 // in: HIP rejects waiting on an event whose stream was destroyed -- an exited
 // thread's hipStreamPerThread gave hipErrorCapturedEvent (907) on the box.)
-struct StreamWs {
-  hipStream_t stream = nullptr;
-  std::thread::id tid;               // owning thread for hipStreamPerThread, else none
-  bool in_use = false;
-  bool captured = false;             // used while its stream was capturing
-  bool retired = false;              // released after a capture, or its thread exited
-  bool cap_now = false;              // the current call's stream is capturing
-  unsigned long long *ws = nullptr;  // kWsRegions x kWsWords u64
-  double *lnl_partials = nullptr;    // kLnlMaxGrid doubles
-  unsigned long long *lnl_ticket = nullptr;
-  // tip/tip protein combination tables (kTtEntryBytes): allocated with the
-  // entry, or on first use with PLFX_CTX_LAZY_TABLES (nullptr until then)
-  char *tt = nullptr;
-};
+using plfx::StreamWs;
 constexpr int kWsPool = PLFX_WS_POOL;
 
 struct plfx_ctx {
@@ -68,7 +45,7 @@ struct plfx_ctx {
   int fuse = 3;  // traverse: 3 six-level subtrees before 2's, 2 three-level subtrees +
                  // level pairs, 1 level pairs, 0 none (PLFX_FUSE)
   bool lazy_tables = false;         // PLFX_CTX_LAZY_TABLES
-  std::deque<StreamWs> wss;         // per-stream workspaces (stable addresses)
+  plfx::WsPool wss{hipStreamPerThread};  // per-stream workspaces
   std::vector<void *> ws_blocks;    // their allocations (the pool's, then one per extra entry)
   uint8_t *tt_codes = nullptr;      // the tip/tip tables' two constant 576-code arrays (kTtCodeBytes)
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
@@ -174,40 +151,21 @@ bool capturing(hipStream_t s) {
 std::mutex g_live_mu;
 std::vector<plfx_ctx *> g_live;  // contexts not yet destroyed
 
-void orphan_thread_entries(plfx_ctx *ctx, std::thread::id tid);
+// the calling thread's id for the workspace pool: an address of its own
+thread_local char t_tag;
 
 struct PerThreadEntries {
   std::vector<plfx_ctx *> ctxs;
   ~PerThreadEntries() {
     std::lock_guard<std::mutex> l(g_live_mu);
     for (plfx_ctx *c : ctxs)
-      if (std::find(g_live.begin(), g_live.end(), c) != g_live.end())
-        orphan_thread_entries(c, std::this_thread::get_id());
+      if (std::find(g_live.begin(), g_live.end(), c) != g_live.end()) {
+        std::lock_guard<std::recursive_mutex> lock(c->mu);
+        c->wss.orphan(&t_tag);
+      }
   }
 };
 thread_local PerThreadEntries t_entries;
-
-// the key thread of a stream handle: the calling thread for hipStreamPerThread
-std::thread::id ws_thread(hipStream_t s) {
-  return s == hipStreamPerThread ? std::this_thread::get_id() : std::thread::id();
-}
-
-StreamWs *ws_find(plfx_ctx *ctx, hipStream_t s) {
-  const std::thread::id tid = ws_thread(s);
-  for (StreamWs &w : ctx->wss)
-    if (w.in_use && !w.retired && w.stream == s && w.tid == tid) return &w;
-  return nullptr;
-}
-
-void orphan_thread_entries(plfx_ctx *ctx, std::thread::id tid) {
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  for (StreamWs &w : ctx->wss)
-    if (w.in_use && !w.retired && w.stream == hipStreamPerThread && w.tid == tid) {
-      w.retired = true;
-      w.stream = nullptr;
-      w.tid = std::thread::id();
-    }
-}
 
 void ws_carve(StreamWs &w, void *base, void *tt) {
   char *b = static_cast<char *>(base);
@@ -217,94 +175,67 @@ void ws_carve(StreamWs &w, void *base, void *tt) {
   w.tt = static_cast<char *>(tt);
 }
 
-// An entry taken by stream s: keyed to it, marked if s is capturing, and for
-// hipStreamPerThread remembered by the calling thread (retired at its exit).
-StreamWs *ws_take(plfx_ctx *ctx, StreamWs &w, hipStream_t s) {
-  w.in_use = true;
-  w.retired = false;
-  w.captured = false;
-  w.stream = s;
-  w.tid = ws_thread(s);
-  if (s == hipStreamPerThread &&
-      std::find(t_entries.ctxs.begin(), t_entries.ctxs.end(), ctx) == t_entries.ctxs.end())
-    t_entries.ctxs.push_back(ctx);
-  return &w;
-}
-
-// The workspace of stream s: its own, else a free pool entry (zero at rest),
-// else a retired per-thread entry reclaimed after a device synchronisation,
-// else a new allocation (zeroed in order on s) -- neither of the last two
-// inside a stream capture.  An entry used while s is capturing is marked: the
-// graph keeps using it after the capture.
-StreamWs *ws_for(plfx_ctx *ctx, hipStream_t s, int *rc) {
-  *rc = PLFX_OK;
-  const bool cap = capturing(s);
-  StreamWs *got = ws_find(ctx, s);
-  if (!got)
-    for (StreamWs &w : ctx->wss)
-      if (!w.in_use) {
-        got = ws_take(ctx, w, s);
-        break;
-      }
-  if (!got && !cap) {
-    // entries of exited threads' per-thread streams (not captured: those
-    // stay retired): their last launches must be done before reuse, and the
-    // thread's stream is gone -- so the device is waited for
-    bool any = false;
-    for (StreamWs &w : ctx->wss) any |= w.in_use && w.retired && !w.captured;
-    if (any) {
-      hipError_t e = hipDeviceSynchronize();
-      if (e != hipSuccess) {
-        *rc = hip_fail(ctx, e, "reclaiming workspaces of exited threads");
-        return nullptr;
-      }
-      for (StreamWs &w : ctx->wss)
-        if (w.in_use && w.retired && !w.captured) w.in_use = false;
-      for (StreamWs &w : ctx->wss)
-        if (!w.in_use) {
-          got = ws_take(ctx, w, s);
-          break;
-        }
-    }
-  }
-  if (got) {
-    got->captured = got->captured || cap;
-    got->cap_now = cap;
-    return got;
-  }
-  if ((int)ctx->wss.size() >= PLFX_MAX_STREAMS) {
-    *rc = fail(ctx, PLFX_ERR_INVALID,
-               "more than %d streams in use with one context (release idle ones with "
-               "plfx_ctx_release_stream)", PLFX_MAX_STREAMS);
-    return nullptr;
-  }
-  if (cap) {
-    *rc = fail(ctx, PLFX_ERR_INVALID,
-               "more than %d streams in use and this one is being captured: issue one call on "
-               "the stream before capturing (its reduction workspace is allocated then)", kWsPool);
-    return nullptr;
-  }
-  // stream-ordered on s: usable by s's next launch with no host wait (and
-  // freed stream-ordered at destroy, which a plain hipFree would turn into a
-  // wait for the whole device)
+// A further entry, allocated and zeroed stream-ordered on s: usable by s's
+// next launch with no host wait (and freed stream-ordered at destroy, which a
+// plain hipFree would turn into a wait for the whole device)
+int ws_allocate(plfx_ctx *ctx, hipStream_t s) {
   void *block = nullptr;
   const size_t bytes = kWsEntryBytes + (ctx->lazy_tables ? 0 : kTtEntryBytes);
   hipError_t e = hipMallocAsync(&block, bytes, s);
-  if (e != hipSuccess) {
-    *rc = fail(ctx, PLFX_ERR_NOMEM, "workspace hipMallocAsync(%zu): %s", bytes, hipGetErrorString(e));
-    return nullptr;
-  }
+  if (e != hipSuccess)
+    return fail(ctx, PLFX_ERR_NOMEM, "workspace hipMallocAsync(%zu): %s", bytes, hipGetErrorString(e));
   e = hipMemsetAsync(block, 0, kWsEntryBytes, s);
   if (e != hipSuccess) {
     (void)hipFreeAsync(block, s);
-    *rc = hip_fail(ctx, e, "workspace memset");
-    return nullptr;
+    return hip_fail(ctx, e, "workspace memset");
   }
   ctx->ws_blocks.push_back(block);
   StreamWs w;
   ws_carve(w, block, ctx->lazy_tables ? nullptr : static_cast<char *>(block) + kWsEntryBytes);
-  ctx->wss.push_back(w);
-  return ws_take(ctx, ctx->wss.back(), s);
+  ctx->wss.add(w);
+  return PLFX_OK;
+}
+
+// The workspace of stream s: its own, else a free pool entry (zero at rest),
+// else a retired per-thread entry reclaimed after a device synchronisation,
+// else a new allocation -- neither of the last two inside a stream capture
+// (WsPool::acquire decides).  A hipStreamPerThread entry is remembered by the
+// thread that takes it (retired at its exit).
+StreamWs *ws_for(plfx_ctx *ctx, hipStream_t s, int *rc) {
+  *rc = PLFX_OK;
+  const bool cap = capturing(s);
+  for (;;) {
+    const plfx::WsPool::Acquired a = ctx->wss.acquire(s, &t_tag, cap);
+    switch (a.answer) {
+      case plfx::WsPool::kTaken:
+        if (s == hipStreamPerThread &&
+            std::find(t_entries.ctxs.begin(), t_entries.ctxs.end(), ctx) == t_entries.ctxs.end())
+          t_entries.ctxs.push_back(ctx);
+        [[fallthrough]];
+      case plfx::WsPool::kHeld:
+        return a.entry;
+      case plfx::WsPool::kReclaim:
+        if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
+          *rc = hip_fail(ctx, e, "reclaiming workspaces of exited threads");
+        else
+          ctx->wss.reclaim();
+        break;
+      case plfx::WsPool::kAllocate:
+        *rc = ws_allocate(ctx, s);
+        break;
+      case plfx::WsPool::kTooMany:
+        *rc = fail(ctx, PLFX_ERR_INVALID,
+                   "more than %d streams in use with one context (release idle ones with "
+                   "plfx_ctx_release_stream)", PLFX_MAX_STREAMS);
+        break;
+      case plfx::WsPool::kCapturing:
+        *rc = fail(ctx, PLFX_ERR_INVALID,
+                   "more than %d streams in use and this one is being captured: issue one call on "
+                   "the stream before capturing (its reduction workspace is allocated then)", kWsPool);
+        break;
+    }
+    if (*rc != PLFX_OK) return nullptr;  // else an entry is free now: acquire again
+  }
 }
 
 // the workspace of stream s as `out`; returns from the caller on failure
@@ -537,16 +468,31 @@ struct TabRef {
   const uint8_t *ca, *cb;
 };
 
+// What the batches of one call share: the entry point's arguments.
+struct BatchCall {
+  int dtype, states, flags;
+  const void *EV;
+  int64_t n;
+  const int32_t *wgt;
+  const void *tipvec;  // may be NULL
+  hipStream_t s;
+  int streams;  // DNA batches share the resident grid with the batches of this many streams in flight
+};
+
 // Nodes of one kind (tips = number of tip children, tip child first) in
 // launches of kMaxBatch.  A tip child is a uint8 code array (no alignment rule).
-// *launches counts the kernel launches issued (may be NULL).  *tabs (may be
-// NULL) receives the tip/tip protein nodes whose tables are still in the
-// stream's workspace afterwards (the last launch group's).
-int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, const void *EV,
-               int64_t n, const int32_t *wgt, hipStream_t s, int tips,
-               const void *tipvec = nullptr, int states = 4, int flags = PLFX_EXACT,
-               int *launches = nullptr, std::vector<TabRef> *tabs = nullptr,
-               const int *ids = nullptr, int streams = 1) {
+// ids (may be NULL) names the nodes in messages (the op indices in a
+// traversal).  *launches counts the kernel launches issued (may be NULL).
+// *tabs (may be NULL) receives the tip/tip protein nodes whose tables are
+// still in the stream's workspace afterwards (the last launch group's).
+int batch_impl(plfx_ctx *ctx, const BatchCall &call, const plfx_node *nodes, int count, int tips,
+               const int *ids = nullptr, int *launches = nullptr, std::vector<TabRef> *tabs = nullptr) {
+  const int dtype = call.dtype, states = call.states;
+  const bool fma = (call.flags & PLFX_FMA) != 0;
+  const void *EV = call.EV, *tipvec = call.tipvec;
+  const int64_t n = call.n;
+  const int32_t *wgt = call.wgt;
+  hipStream_t s = call.s;
   if (tabs) tabs->clear();
   if (count < 0 || n < 0 || (count > 0 && (!nodes || !EV)))
     return fail(ctx, PLFX_ERR_INVALID, "bad batch arguments");
@@ -562,49 +508,47 @@ int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, cons
     // both children coded tips: the node's 576 code pairs through its own
     // kernel, then x3 / scaler / sum gathered by code pair (a write stream;
     // the direct kernel is compute-bound: 77 us f64, 95 us f32 per 2^18 sites)
-    {
-      if (!w->tt) {  // PLFX_CTX_LAZY_TABLES: this entry's tables on its first tip/tip use
-        if (w->cap_now)
-          return fail(ctx, PLFX_ERR_INVALID,
-                      "protein tip/tip tables: the context was created with PLFX_CTX_LAZY_TABLES and "
-                      "this stream has not made a tip/tip call outside a capture yet");
-        void *t = nullptr;
-        hipError_t e = hipMallocAsync(&t, kTtEntryBytes, s);
-        if (e != hipSuccess)
-          return fail(ctx, PLFX_ERR_NOMEM, "tip/tip tables hipMallocAsync(%zu): %s", kTtEntryBytes,
-                      hipGetErrorString(e));
-        ctx->ws_blocks.push_back(t);
-        w->tt = static_cast<char *>(t);
-      }
-      char *tt = w->tt;
-      const uint8_t *cc1 = ctx->tt_codes, *cc2 = cc1 + 1024;
-      for (int j = 0; j < count; j += plfx::kMaxBatch) {
-        const int c = std::min(count - j, plfx::kMaxBatch);
-        plfx::NodeDescH comb[plfx::kMaxBatch];
-        plfx::ProtGatherDescH g[plfx::kMaxBatch];
-        for (int i = 0; i < c; i++) {
-          const plfx_node &d = nodes[j + i];
-          char *tab = tt + (size_t)i * (kTtTabBytes + kTtScBytes);
-          uint8_t *tsc = reinterpret_cast<uint8_t *>(tab + kTtTabBytes);
-          comb[i] = plfx::NodeDescH{cc1, cc2, tab, d.left, d.right, tsc, nullptr};
-          g[i] = plfx::ProtGatherDescH{static_cast<const uint8_t *>(d.x1), static_cast<const uint8_t *>(d.x2),
-                                       d.x3, d.scaler, d.scaler_sum, tab, tsc};
-        }
-        hipError_t e = plfx::launch_plf_prot_batch(dtype, (flags & PLFX_FMA) != 0, comb, c, EV, nullptr,
-                                                   plfx::kProtCombos, w->ws, ctx->max_blocks, s, 2, tipvec);
-        if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot combination tables");
-        e = plfx::launch_prot_tiptip_gather(dtype, g, c, wgt, n, w->ws, ctx->max_blocks, s);
-        if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot tip/tip gather");
-        if (launches) *launches += 2;
-        if (tabs) {  // this group's tables stay until the next group overwrites them
-          tabs->clear();
-          for (int i = 0; i < c; i++)
-            tabs->push_back(TabRef{nodes[j + i].x3, comb[i].x3, static_cast<const uint8_t *>(nodes[j + i].x1),
-                                   static_cast<const uint8_t *>(nodes[j + i].x2)});
-        }
-      }
-      return PLFX_OK;
+    if (!w->tt) {  // PLFX_CTX_LAZY_TABLES: this entry's tables on its first tip/tip use
+      if (w->capturing_now())
+        return fail(ctx, PLFX_ERR_INVALID,
+                    "protein tip/tip tables: the context was created with PLFX_CTX_LAZY_TABLES and "
+                    "this stream has not made a tip/tip call outside a capture yet");
+      void *t = nullptr;
+      hipError_t e = hipMallocAsync(&t, kTtEntryBytes, s);
+      if (e != hipSuccess)
+        return fail(ctx, PLFX_ERR_NOMEM, "tip/tip tables hipMallocAsync(%zu): %s", kTtEntryBytes,
+                    hipGetErrorString(e));
+      ctx->ws_blocks.push_back(t);
+      w->tt = static_cast<char *>(t);
     }
+    char *tt = w->tt;
+    const uint8_t *cc1 = ctx->tt_codes, *cc2 = cc1 + 1024;
+    for (int j = 0; j < count; j += plfx::kMaxBatch) {
+      const int c = std::min(count - j, plfx::kMaxBatch);
+      plfx::NodeDescH comb[plfx::kMaxBatch];
+      plfx::ProtGatherDescH g[plfx::kMaxBatch];
+      for (int i = 0; i < c; i++) {
+        const plfx_node &d = nodes[j + i];
+        char *tab = tt + (size_t)i * (kTtTabBytes + kTtScBytes);
+        uint8_t *tsc = reinterpret_cast<uint8_t *>(tab + kTtTabBytes);
+        comb[i] = plfx::NodeDescH{cc1, cc2, tab, d.left, d.right, tsc, nullptr};
+        g[i] = plfx::ProtGatherDescH{static_cast<const uint8_t *>(d.x1), static_cast<const uint8_t *>(d.x2),
+                                     d.x3, d.scaler, d.scaler_sum, tab, tsc};
+      }
+      hipError_t e = plfx::launch_plf_prot_batch(dtype, fma, comb, c, EV, nullptr, plfx::kProtCombos, w->ws,
+                                                 ctx->max_blocks, s, 2, tipvec);
+      if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot combination tables");
+      e = plfx::launch_prot_tiptip_gather(dtype, g, c, wgt, n, w->ws, ctx->max_blocks, s);
+      if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot tip/tip gather");
+      if (launches) *launches += 2;
+      if (tabs) {  // this group's tables stay until the next group overwrites them
+        tabs->clear();
+        for (int i = 0; i < c; i++)
+          tabs->push_back(TabRef{nodes[j + i].x3, comb[i].x3, static_cast<const uint8_t *>(nodes[j + i].x1),
+                                 static_cast<const uint8_t *>(nodes[j + i].x2)});
+      }
+    }
+    return PLFX_OK;
   }
   if (states == 20 && count > 1) {
     // protein: up to kMaxBatch nodes per launch, node = blockIdx.y, each node
@@ -618,8 +562,8 @@ int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, cons
     const plfx::NodeDescH *all = reinterpret_cast<const plfx::NodeDescH *>(nodes);
     for (int j = 0; j < count; j += plfx::kMaxBatch) {
       const int c = std::min(count - j, plfx::kMaxBatch);
-      hipError_t e = plfx::launch_plf_prot_batch(dtype, (flags & PLFX_FMA) != 0, all + j, c, EV, wgt, n,
-                                                 w->ws, ctx->max_blocks, s, tips, tipvec);
+      hipError_t e = plfx::launch_plf_prot_batch(dtype, fma, all + j, c, EV, wgt, n, w->ws, ctx->max_blocks,
+                                                 s, tips, tipvec);
       if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot batch launch");
       if (launches) ++*launches;
     }
@@ -628,8 +572,7 @@ int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, cons
   if (states == 20) {  // protein, one node: one full-GPU launch (plf_prot.hpp)
     const plfx_node &d = nodes[0];
     plfx::DnaArgs a{d.x1, d.x2, d.x3, EV, d.left, d.right, wgt, d.scaler, d.scaler_sum, w->ws, n};
-    hipError_t e = plfx::launch_plf_prot(dtype, (flags & PLFX_FMA) != 0, a, ctx->max_blocks, s, tips,
-                                         tipvec);
+    hipError_t e = plfx::launch_plf_prot(dtype, fma, a, ctx->max_blocks, s, tips, tipvec);
     if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot launch");
     if (launches) ++*launches;
     return PLFX_OK;
@@ -648,11 +591,40 @@ int batch_impl(plfx_ctx *ctx, int dtype, const plfx_node *nodes, int count, cons
     int c = 0;
     for (int i = j; i < count; i += L) sel[c++] = all[i];
     hipError_t e = plfx::launch_plf_dna_batch(dtype, L == 1 ? all : sel, c, EV, wgt, n, w->ws,
-                                              ctx->max_blocks, s, tips, tipvec, streams);
+                                              ctx->max_blocks, s, tips, tipvec, call.streams);
     if (e != hipSuccess) return hip_fail(ctx, e, "plf batch launch");
     if (launches) ++*launches;
   }
   return PLFX_OK;
+}
+
+// The environment's settings of a new context; false for a value that is refused.
+bool env_settings(plfx_ctx *ctx) {
+  // Grid cap: 0 = as many blocks as are co-resident (occupancy x CUs);
+  // PLFX_MAX_BLOCKS overrides it for experiments.
+  if (const char *env = std::getenv("PLFX_MAX_BLOCKS")) {
+    int v = std::atoi(env);
+    if (v > 0) ctx->max_blocks = v;
+  }
+  if (const char *env = std::getenv("PLFX_FUSE")) ctx->fuse = std::atoi(env);
+  // PLFX_NODE_SEGMENTS: "1" on, "0" off, "-1" / "auto" / unset by size; any
+  // other value is refused (a typo must not silently switch the mapping)
+  if (const char *env = std::getenv("PLFX_NODE_SEGMENTS")) {
+    if (!std::strcmp(env, "1")) ctx->node_segments = 1;
+    else if (!std::strcmp(env, "0")) ctx->node_segments = 0;
+    else if (!std::strcmp(env, "-1") || !std::strcmp(env, "auto") || !*env) ctx->node_segments = -1;
+    else return false;
+  }
+  // PLFX_STREAMS: one-node calls kept in flight, "1".."8" (PLFX_STREAMS_MAX), empty
+  // = 1; anything else is refused like PLFX_NODE_SEGMENTS
+  const char *env = std::getenv("PLFX_STREAMS");
+  if (env && *env) {
+    static_assert(PLFX_STREAMS_MAX <= 9, "PLFX_STREAMS is parsed as one digit");
+    const int v = (env[0] >= '1' && env[0] <= '0' + PLFX_STREAMS_MAX && !env[1]) ? env[0] - '0' : 0;
+    if (!v) return false;
+    ctx->streams = v;
+  }
+  return true;
 }
 
 }  // namespace
@@ -678,42 +650,13 @@ int plfx_ctx_create_ex(int device, unsigned flags, plfx_ctx **out) {
   ctx->device = device;
   ctx->lazy_tables = (flags & PLFX_CTX_LAZY_TABLES) != 0;
   DeviceGuard guard(device);  // the caller's current device is restored on return
-  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+  // the settings first: until the stream exists only the context is to undo
+  int rc = PLFX_OK;
+  if (!env_settings(ctx)) rc = PLFX_ERR_INVALID;
+  else if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) rc = PLFX_ERR_HIP;
+  if (rc != PLFX_OK) {
     delete ctx;
-    return PLFX_ERR_HIP;
-  }
-  // Grid cap: 0 = as many blocks as are co-resident (occupancy x CUs);
-  // PLFX_MAX_BLOCKS overrides it for experiments.
-  if (const char *env = std::getenv("PLFX_MAX_BLOCKS")) {
-    int v = std::atoi(env);
-    if (v > 0) ctx->max_blocks = v;
-  }
-  if (const char *env = std::getenv("PLFX_FUSE")) ctx->fuse = std::atoi(env);
-  // PLFX_NODE_SEGMENTS: "1" on, "0" off, "-1" / "auto" / unset by size; any
-  // other value is refused (a typo must not silently switch the mapping)
-  if (const char *env = std::getenv("PLFX_NODE_SEGMENTS")) {
-    if (!std::strcmp(env, "1")) ctx->node_segments = 1;
-    else if (!std::strcmp(env, "0")) ctx->node_segments = 0;
-    else if (!std::strcmp(env, "-1") || !std::strcmp(env, "auto") || !*env) ctx->node_segments = -1;
-    else {
-      (void)hipStreamDestroy(ctx->stream);
-      delete ctx;
-      return PLFX_ERR_INVALID;
-    }
-  }
-  // PLFX_STREAMS: one-node calls kept in flight, "1".."8" (PLFX_STREAMS_MAX), empty
-  // = 1; anything else is refused like PLFX_NODE_SEGMENTS
-  const char *streams_env = std::getenv("PLFX_STREAMS");
-  if (streams_env && *streams_env) {
-    const char *env = streams_env;
-    static_assert(PLFX_STREAMS_MAX <= 9, "PLFX_STREAMS is parsed as one digit");
-    const int v = (env[0] >= '1' && env[0] <= '0' + PLFX_STREAMS_MAX && !env[1]) ? env[0] - '0' : 0;
-    if (!v) {
-      (void)hipStreamDestroy(ctx->stream);
-      delete ctx;
-      return PLFX_ERR_INVALID;
-    }
-    ctx->streams = v;
+    return rc;
   }
   // the workspace pool: kWsPool entries (reduction words zeroed before return,
   // tip/tip tables), and the tables' constant code arrays
@@ -747,7 +690,7 @@ int plfx_ctx_create_ex(int device, unsigned flags, plfx_ctx **out) {
     StreamWs w;
     ws_carve(w, static_cast<char *>(pool) + i * kWsEntryBytes,
              tabs ? static_cast<char *>(tabs) + i * kTtEntryBytes : nullptr);
-    ctx->wss.push_back(w);
+    ctx->wss.add(w);
   }
   {
     std::lock_guard<std::mutex> l(g_live_mu);
@@ -785,10 +728,7 @@ int plfx_ctx_destroy(plfx_ctx *ctx) {
     // waited for; releasing streams (plfx_ctx_release_stream) before destroy
     // avoids that wait.  An entry used under a capture needs it anyway (its
     // graph may still be replaying on any stream).
-    bool device_wide = false;
-    for (StreamWs &w : ctx->wss)
-      if (w.in_use && (w.captured || w.retired || w.stream != ctx->stream)) device_wide = true;
-    if (device_wide) (void)hipDeviceSynchronize();
+    if (ctx->wss.needs_device_wait(ctx->stream)) (void)hipDeviceSynchronize();
     for (void *b : ctx->ws_blocks) (void)hipFreeAsync(b, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamDestroy(ctx->stream);
@@ -820,7 +760,7 @@ int plfx_ctx_synchronize(plfx_ctx *ctx) {
 int plfx_ctx_release_stream(plfx_ctx *ctx, void *stream) {
   PLFX_BIND(ctx);
   hipStream_t s = pick(stream);
-  StreamWs *w = ws_find(ctx, s);
+  StreamWs *w = ctx->wss.find(s, &t_tag);
   if (!w) return PLFX_OK;  // no workspace held: nothing to release
   if (capturing(s))  // a wait on a capturing stream would invalidate the capture
     return fail(ctx, PLFX_ERR_INVALID, "stream is being captured: release it after the capture ends");
@@ -829,10 +769,7 @@ int plfx_ctx_release_stream(plfx_ctx *ctx, void *stream) {
   PLFX_HIP(ctx, hipStreamSynchronize(s));
   // a graph captured through the entry keeps using its words (sum tickets,
   // queue heads, tip/tip tables): retired, never handed to another stream
-  if (w->captured) w->retired = true;
-  else w->in_use = false;
-  w->stream = nullptr;
-  w->tid = std::thread::id();
+  ctx->wss.release(w);
   return PLFX_OK;
 }
 
@@ -972,8 +909,8 @@ int plfx_plf_batch_dev(plfx_ctx *ctx, int dtype, int states, const plfx_node *no
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "batched nodes: states=%d not built (4, 20)", states);
   // DNA batches share the resident grid with the batches of the other
   // streams in flight (plfx_ctx_set_streams)
-  return batch_impl(ctx, dtype, nodes, count, EV, n, wgt, pick(stream), 0, nullptr, states,
-                    PLFX_EXACT, nullptr, nullptr, nullptr, ctx->streams);
+  const BatchCall call{dtype, states, PLFX_EXACT, EV, n, wgt, /*tipvec*/ nullptr, pick(stream), ctx->streams};
+  return batch_impl(ctx, call, nodes, count, 0);
 }
 
 int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const uint8_t *tip1,
@@ -995,7 +932,8 @@ int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const
     std::swap(nd.x1, nd.x2);
     std::swap(nd.left, nd.right);
   }
-  return batch_impl(ctx, dtype, &nd, 1, EV, n, wgt, pick(stream), tips, tipvec, states, flags);
+  const BatchCall call{dtype, states, flags, EV, n, wgt, tipvec, pick(stream), /*streams*/ 1};
+  return batch_impl(ctx, call, &nd, 1, tips);
 }
 
 int plfx_plf_tips_dev(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1,
@@ -1067,6 +1005,7 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   // levels may overwrite the tables or the children's slots.
   std::vector<TabRef> prev_tabs, cur_tabs;
   const bool tab_mode = states == 20;
+  const BatchCall call{dtype, states, flags, EV, n, wgt, tipvec, s, /*streams*/ 1};
   for (int lv = 0; lv < plan.nlev; lv++) {
     for (int k = 0; k < 3; k++) {
       batch[k].clear();
@@ -1164,9 +1103,8 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
         bop[0].swap(rest_op);
       }
       if (batch[k].empty()) continue;
-      int rc = batch_impl(ctx, dtype, batch[k].data(), (int)batch[k].size(), EV, n, wgt, s, k,
-                          tipvec, states, flags, &sched[6], k == 2 && tab_mode ? &cur_tabs : nullptr,
-                          bop[k].data());
+      int rc = batch_impl(ctx, call, batch[k].data(), (int)batch[k].size(), k, bop[k].data(), &sched[6],
+                          k == 2 && tab_mode ? &cur_tabs : nullptr);
       if (rc != PLFX_OK) return rc;
     }
     prev_tabs.swap(cur_tabs);
