@@ -92,12 +92,25 @@ hipError_t launch_plf_prot_batch(int dtype, bool fma, const NodeDescH *nodes, in
                                  const int32_t *wgt, int64_t n, unsigned long long *ws, int max_blocks,
                                  hipStream_t s, int tips, const void *tipvec);
 
-// Root log-likelihood; partials: >= kLnlMaxGrid doubles; ticket: kWsWords u64 (zero at rest).
+// Root log-likelihood; partials: >= kLnlMaxGrid doubles (one accumulator); ticket: kWsWords u64 (zero at rest).
 constexpr int kLnlMaxGrid = 4096;
 hipError_t launch_root_lnl(int dtype, int states, const void *x, int64_t n, const double *catw,
                            const double *freq, const int32_t *wgt, const int64_t *scaler_sums,
                            int nsums, double *partials, unsigned long long *ticket, double *out,
                            double *site_lnl, hipStream_t s);
+
+// One branch between two fixed CLVs (plf_edge.hpp; defined in plf_edge.hip =
+// libplfx_edge.so, which libplfx.so links).  Sum table: tip != 0 reads
+// x1 as uint8 codes through tipvec (required then).  Derivatives: partials
+// >= 3 * kLnlMaxGrid doubles, ticket as launch_root_lnl's; lambda, rates (4),
+// t: device f64; out: 3 device doubles.
+hipError_t launch_edge_sumtable(int dtype, int states, bool tip, const void *x1, const void *x2, int64_t n,
+                                const void *tipvec, void *sumtab, int max_blocks, hipStream_t s);
+hipError_t launch_edge_derivatives(int dtype, int states, const void *sumtab, int64_t n, const double *lambda,
+                                   const double *rates, const double *catw, const int32_t *wgt,
+                                   const double *t, const int64_t *scaler_sums, int nsums, double *partials,
+                                   unsigned long long *ticket, double *out3, double *site_lnl,
+                                   int max_blocks, hipStream_t s);
 
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,

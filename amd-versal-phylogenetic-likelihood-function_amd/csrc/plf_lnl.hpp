@@ -26,26 +26,38 @@ namespace dev {
 
 constexpr double kLogMinLik = -22.18070977791824990137;  // log(2^-32) = -32 ln 2
 
-// The fixed-order cross-block part of the root lnL (both kernels): the block's
-// lanes' acc into a fixed slot, the last block (two-level election) sums the
-// slots in index order and adds the scaler correction.
-__device__ __forceinline__ void lnl_finish(double acc, double *partials, unsigned long long *ticket, double *out,
-                                  const int64_t *__restrict__ scaler_sums, int nsums) {
+// The fixed-order cross-block part of the root lnL (both kernels) and of the
+// edge derivatives (plf_edge.hpp, N = 3): the block's lanes' N accumulators
+// into fixed slots (accumulator j of block b at partials[j * gridDim.x + b]),
+// the last block (two-level election) sums each accumulator's slots in index
+// order; out[0] also gets the scaler correction.
+template <int N>
+__device__ __forceinline__ void lnl_finish(double (&acc)[N], double *partials, unsigned long long *ticket,
+                                           double *out, const int64_t *__restrict__ scaler_sums, int nsums) {
   const int lane = threadIdx.x & 63;
   // fixed-order block reduction
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  __shared__ double part[kWavesPerBlock];
+  for (int j = 0; j < N; j++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off);
+  }
+  __shared__ double part[N][kWavesPerBlock];
   __shared__ int last;
-  if (lane == 0) part[threadIdx.x >> 6] = acc;
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < N; j++) part[j][threadIdx.x >> 6] = acc[j];
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double b = 0.0;
 #pragma unroll
-    for (int i = 0; i < kWavesPerBlock; i++) b += part[i];
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(partials) + blockIdx.x,
-                       __builtin_bit_cast(unsigned long long, b), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
+    for (int j = 0; j < N; j++) {
+      double b = 0.0;
+#pragma unroll
+      for (int i = 0; i < kWavesPerBlock; i++) b += part[j][i];
+      __hip_atomic_store(reinterpret_cast<unsigned long long *>(partials) + (size_t)j * gridDim.x + blockIdx.x,
+                         __builtin_bit_cast(unsigned long long, b), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // two-level election (a single counter serialises ~12 ns per arrival:
     // 20 us for 1800 blocks): slot counters 128 B apart, then a top counter;
@@ -64,25 +76,42 @@ __device__ __forceinline__ void lnl_finish(double acc, double *partials, unsigne
   }
   __syncthreads();
   if (!last) return;
-  double v = 0.0;
-  for (unsigned i = threadIdx.x; i < gridDim.x; i += kBlock)
-    v += __builtin_bit_cast(double, __hip_atomic_load(
-                                        reinterpret_cast<unsigned long long *>(partials) + i,
-                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  double v[N];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  for (int j = 0; j < N; j++) {
+    v[j] = 0.0;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += kBlock)
+      v[j] += __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<unsigned long long *>(partials) +
+                                                               (size_t)j * gridDim.x + i,
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[j] += __shfl_xor(v[j], off);
+  }
   __syncthreads();
-  if (lane == 0) part[threadIdx.x >> 6] = v;
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < N; j++) part[j][threadIdx.x >> 6] = v[j];
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < kWavesPerBlock; i++) tot += part[i];
     long long nsc = 0;
     for (int i = 0; i < nsums; i++) nsc += scaler_sums[i];
-    *out = tot + (double)nsc * kLogMinLik;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+      double tot = 0.0;
+#pragma unroll
+      for (int i = 0; i < kWavesPerBlock; i++) tot += part[j][i];
+      out[j] = j == 0 ? tot + (double)nsc * kLogMinLik : tot;
+    }
     __hip_atomic_store(ticket + kSlots * 16, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// one accumulator: the root lnL
+__device__ __forceinline__ void lnl_finish(double acc, double *partials, unsigned long long *ticket, double *out,
+                                           const int64_t *__restrict__ scaler_sums, int nsums) {
+  double a[1] = {acc};
+  lnl_finish<1>(a, partials, ticket, out, scaler_sums, nsums);
 }
 
 // C lanes per site (lane = category); S states per lane.  A loop trip covers C

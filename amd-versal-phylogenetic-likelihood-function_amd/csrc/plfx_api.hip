@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/plfx.h"
+#include "edge_newton.hpp"
 #include "plf_kernels.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
@@ -48,6 +49,7 @@ struct plfx_ctx {
   plfx::WsPool wss{hipStreamPerThread};  // per-stream workspaces
   std::vector<void *> ws_blocks;    // their allocations (the pool's, then one per extra entry)
   uint8_t *tt_codes = nullptr;      // the tip/tip tables' two constant 576-code arrays (kTtCodeBytes)
+  double *edge_buf = nullptr;       // plfx_edge_optimize: the trial t and the three results (kEdgeBufBytes)
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
@@ -87,7 +89,9 @@ struct DeviceGuard {
 constexpr size_t kWsRegions = std::max({(size_t)plfx::kMaxBatch, (size_t)7 * plfx::kMaxSeptets,
                                         (size_t)plfx::kDeepNodes, (size_t)plfx::kDeepQueueRegion + 1});
 constexpr size_t kWsBytes = kWsRegions * plfx::kWsWords * sizeof(unsigned long long);
-constexpr size_t kLnlPartialBytes = plfx::kLnlMaxGrid * sizeof(double);
+// three accumulators per block (the edge derivatives; the root lnL uses the first kLnlMaxGrid)
+constexpr size_t kLnlPartialBytes = 3 * (size_t)plfx::kLnlMaxGrid * sizeof(double);
+constexpr size_t kEdgeBufBytes = 4 * sizeof(double);
 constexpr size_t kLnlTicketBytes = plfx::kWsWords * sizeof(unsigned long long);
 
 int fail(plfx_ctx *ctx, int code, const char *fmt, ...) {
@@ -627,6 +631,18 @@ bool env_settings(plfx_ctx *ctx) {
   return true;
 }
 
+// the arguments plfx_edge_derivatives and plfx_edge_optimize share
+int check_edge_args(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                           const double *eigen, const double *rates, int ncat) {
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (states != 4 && states != 20) return fail(ctx, PLFX_ERR_UNSUPPORTED, "edge: states=%d not built (4, 20)", states);
+  if (ncat != 4) return fail(ctx, PLFX_ERR_UNSUPPORTED, "edge: ncat=%d not built (4)", ncat);
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  if (!eigen || !rates || (n > 0 && !sumtab)) return fail(ctx, PLFX_ERR_INVALID, "edge: null sum table / eigen / rates");
+  if (!aligned16(sumtab)) return fail(ctx, PLFX_ERR_INVALID, "the sum table must be 16-byte aligned");
+  return PLFX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,7 +683,7 @@ int plfx_ctx_create_ex(int device, unsigned flags, plfx_ctx **out) {
     delete ctx;
     return code;
   };
-  void *pool = nullptr, *tabs = nullptr, *codes = nullptr;
+  void *pool = nullptr, *tabs = nullptr, *codes = nullptr, *edge = nullptr;
   if (hipMallocAsync(&pool, kWsPool * kWsEntryBytes, ctx->stream) != hipSuccess) return undo(PLFX_ERR_NOMEM);
   ctx->ws_blocks.push_back(pool);
   if (!ctx->lazy_tables) {
@@ -676,6 +692,9 @@ int plfx_ctx_create_ex(int device, unsigned flags, plfx_ctx **out) {
   }
   if (hipMallocAsync(&codes, kTtCodeBytes, ctx->stream) != hipSuccess) return undo(PLFX_ERR_NOMEM);
   ctx->ws_blocks.push_back(codes);
+  if (hipMallocAsync(&edge, kEdgeBufBytes, ctx->stream) != hipSuccess) return undo(PLFX_ERR_NOMEM);
+  ctx->ws_blocks.push_back(edge);
+  ctx->edge_buf = static_cast<double *>(edge);
   uint8_t cc[kTtCodeBytes] = {};
   for (int k = 0; k < plfx::kProtCombos; k++) {
     cc[k] = (uint8_t)(k / 24);
@@ -1169,6 +1188,79 @@ int plfx_pmatrix(plfx_ctx *ctx, int dtype, int states, int convention, const dou
   hipError_t e = plfx::launch_pmatrix(dtype, convention == PLFX_PMAT_EIGEN, eigen, states, rates,
                                       ncat, blen, nbranch, pmats, pick(stream));
   if (e != hipSuccess) return hip_fail(ctx, e, "pmatrix launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                       const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (states != 4 && states != 20)
+    return fail(ctx, PLFX_ERR_UNSUPPORTED, "edge_sumtable: states=%d not built (4, 20)", states);
+  if ((tip1 != nullptr) == (x1 != nullptr))
+    return fail(ctx, PLFX_ERR_INVALID, "side 1 needs exactly one of tip / CLV");
+  if (tip1 && !tipvec)
+    return fail(ctx, PLFX_ERR_INVALID, "a coded side needs tipvec (the default 0/1 table is not in eigen coordinates)");
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  if (n == 0) return PLFX_OK;
+  if (!x2 || !sumtab) return fail(ctx, PLFX_ERR_INVALID, "null CLV / sum table pointer");
+  if ((x1 && !aligned16(x1)) || !aligned16(x2) || !aligned16(sumtab))
+    return fail(ctx, PLFX_ERR_INVALID, "CLV pointers must be 16-byte aligned");
+  const size_t cb = clv_bytes_of(dtype, states, n);
+  if (overlap(sumtab, cb, tip1 ? (const void *)tip1 : x1, tip1 ? (size_t)n : cb) || overlap(sumtab, cb, x2, cb))
+    return fail(ctx, PLFX_ERR_INVALID, "sumtab may not overlap x1/x2");
+  hipError_t e = plfx::launch_edge_sumtable(dtype, states, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2,
+                                            n, tipvec, sumtab, ctx->max_blocks, pick(stream));
+  if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_derivatives(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                          const double *eigen, const double *rates, int ncat, const double *catw,
+                          const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                          double *out3, double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_edge_args(ctx, dtype, states, sumtab, n, eigen, rates, ncat); rc != PLFX_OK) return rc;
+  if (!t || !out3 || nsums < 0 || (nsums > 0 && !scaler_sums))
+    return fail(ctx, PLFX_ERR_INVALID, "bad edge_derivatives arguments");
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // n == 0 launches too: one block, out3 = {correction, 0, 0}
+  hipError_t e = plfx::launch_edge_derivatives(dtype, states, sumtab, n, eigen, rates, catw, wgt, t, scaler_sums,
+                                               nsums, w->lnl_partials, w->lnl_ticket, out3, site_lnl,
+                                               ctx->max_blocks, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "edge_derivatives launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                       const double *eigen, const double *rates, int ncat, const double *catw,
+                       const int32_t *wgt, double t0, double tmin, double tmax, int max_evals,
+                       double *t_opt, double *out3_host, int *evals, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_edge_args(ctx, dtype, states, sumtab, n, eigen, rates, ncat); rc != PLFX_OK) return rc;
+  if (!t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize: null t_opt");
+  plfx::EdgeNewton step(t0, tmin, tmax, max_evals);
+  if (!step.valid())
+    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize: needs 0 < tmin <= t0 <= tmax and max_evals >= 1");
+  hipStream_t s = pick(stream);
+  if (capturing(s))
+    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize waits for every evaluation: not on a capturing stream");
+  double *d_t = ctx->edge_buf, *d_out = ctx->edge_buf + 1;
+  double t = 0.0, out[3] = {0.0, 0.0, 0.0};
+  for (bool more = true; more;) {
+    t = step.t();  // read by the upload until the wait below
+    PLFX_HIP(ctx, hipMemcpyAsync(d_t, &t, sizeof t, hipMemcpyHostToDevice, s));
+    int rc = plfx_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, catw, wgt, d_t, nullptr, 0,
+                                   d_out, nullptr, stream);
+    if (rc != PLFX_OK) return rc;
+    PLFX_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, s));
+    PLFX_HIP(ctx, hipStreamSynchronize(s));
+    more = step.advance(out[1], out[2]);
+  }
+  *t_opt = t;
+  if (out3_host) std::copy(out, out + 3, out3_host);
+  if (evals) *evals = step.evals();
   return PLFX_OK;
 }
 

@@ -17,7 +17,7 @@ namespace plfx {
 class StreamWs {
  public:
   unsigned long long *ws = nullptr;  // kWsRegions x kWsWords u64
-  double *lnl_partials = nullptr;    // kLnlMaxGrid doubles
+  double *lnl_partials = nullptr;    // 3 x kLnlMaxGrid doubles (plf_edge.hpp sums three values per block)
   unsigned long long *lnl_ticket = nullptr;
   // tip/tip protein combination tables (kTtEntryBytes): allocated with the
   // entry, or on first use with PLFX_CTX_LAZY_TABLES (nullptr until then)

@@ -53,6 +53,7 @@ EXPORTS = (
     "plfx_model_eigen", "plfx_gamma_rates", "plfx_model_ev", "plfx_model_root_weights",
     "plfx_pmatrix", "plfx_model_tip_vectors",
     "plfx_shard", "plfx_gen_hostmem", "plfx_swemu_instance_run", "plfx_traverse_schedule",
+    "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize",
 )
 MAX_STREAMS = 64   # PLFX_MAX_STREAMS
 WS_POOL = 8        # PLFX_WS_POOL
@@ -160,6 +161,11 @@ def load():
     L.plfx_gen_hostmem.argtypes = [i32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp]
     L.plfx_swemu_instance_run.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, i32, i32, i32]
     L.plfx_traverse_schedule.argtypes = [vp, C.POINTER(i32), i32]
+    L.plfx_edge_sumtable.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, vp, vp]
+    L.plfx_edge_derivatives.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    dbl = C.c_double
+    L.plfx_edge_optimize.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32,
+                                     dp, dp, C.POINTER(i32), vp]
     _lib = L
     return L
 
@@ -628,6 +634,80 @@ class Context:
         self._check(self._L.plfx_root_lnl(self.h, F32 if x.dtype == torch.float32 else F64, states,
                                           p(x), int(n), p(catw), p(freq), p(wgt), p(scaler_sums),
                                           nsums, p(out), p(site_lnl), self._sh(stream)))
+
+    # -- (10) one branch between two fixed CLVs -----------------------------
+    def edge_sumtable(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
+        """sumtab = x1 * x2 elementwise (plfx.h (10)); side 1 is the dense CLV
+        x1 or the uint8 codes tip1 with the eigen-convention table tipvec
+        (16 x 4 DNA, PROT_CODES x 20 protein).  CLVs in the eigen convention."""
+        import torch
+
+        dt = sumtab.dtype
+        V = 4 * states
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
+            if t is not None and (t.dtype != dt or t.numel() < V * n or not t.is_contiguous()
+                                  or not t.is_cuda):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= {V}*n")
+        if tip1 is not None and (tip1.dtype != torch.uint8 or tip1.numel() < n or not tip1.is_contiguous()
+                                 or not tip1.is_cuda):
+            raise PlfxError(ERR_INVALID, "tip1 must be a contiguous uint8 device tensor >= n")
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        self._check(self._L.plfx_edge_sumtable(self.h, F32 if dt == torch.float32 else F64, int(states),
+                                               p(tip1), p(x1), p(x2), int(n),
+                                               self._tipvec(tipvec, dt, states), p(sumtab),
+                                               self._sh(stream)))
+
+    def _edge_args(self, sumtab, n, eigen, rates, catw, wgt, states):
+        import torch
+
+        if (sumtab.dtype not in (torch.float32, torch.float64) or sumtab.numel() < 4 * states * n
+                or not sumtab.is_cuda or not sumtab.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "sumtab must be a contiguous float device tensor of >= 4*S*n values")
+        for k, t, m in (("eigen", eigen, states), ("rates", rates, 1), ("catw", catw, rates.numel())):
+            if t is not None and (t.dtype != torch.float64 or t.numel() < m or not t.is_cuda
+                                  or not t.is_contiguous()):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor")
+        _check_aux(n, wgt, None, None)
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        return (self.h, F32 if sumtab.dtype == torch.float32 else F64, int(states), p(sumtab), int(n),
+                p(eigen), p(rates), rates.numel(), p(catw), p(wgt))
+
+    def edge_derivatives(self, sumtab, n, eigen, rates, t, out, catw=None, wgt=None, scaler_sums=None,
+                         site_lnl=None, states=4, stream=None):
+        """out (float64 device tensor, 3 elements) = lnL, d lnL/dt, d2 lnL/dt2 of
+        the branch whose sum table is `sumtab`, at the branch length in the
+        device double `t`; see plfx.h (10).  eigen, rates: the device arrays
+        pmatrix() takes."""
+        import torch
+
+        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
+        for k, x, m in (("t", t, 1), ("out", out, 3), ("site_lnl", site_lnl, n)):
+            if x is not None and (x.dtype != torch.float64 or x.numel() < m or not x.is_cuda
+                                  or not x.is_contiguous()):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor of >= {m}")
+        if t is None or out is None:
+            raise PlfxError(ERR_INVALID, "t and out are required")
+        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
+                                        or not scaler_sums.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
+        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
+        nsums = 0 if scaler_sums is None else scaler_sums.numel()
+        self._check(self._L.plfx_edge_derivatives(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl),
+                                                  self._sh(stream)))
+
+    def optimize_branch(self, sumtab, n, eigen, rates, t0, tmin=1e-8, tmax=10.0, max_evals=64,
+                        catw=None, wgt=None, states=4, stream=None):
+        """The branch length in [tmin, tmax] maximising the edge lnL, by the
+        bracketed Newton iteration of plfx_edge_optimize from t0 (host-
+        synchronous).  Returns (t, lnL, d1, d2, evals), lnL without a scaling
+        correction."""
+        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
+        t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
+        self._check(self._L.plfx_edge_optimize(*args, float(t0), float(tmin), float(tmax), int(max_evals),
+                                               C.byref(t), out, C.byref(ev), self._sh(stream)))
+        return t.value, out[0], out[1], out[2], ev.value
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):

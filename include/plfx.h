@@ -491,6 +491,67 @@ int plfx_pmatrix(plfx_ctx *ctx, int dtype, int states, int convention, const dou
                  const double *rates, int ncat, const double *blen, int64_t nbranch, void *pmats,
                  void *stream);
 
+/* ---- (10) one branch between two fixed CLVs: the sum table, the edge
+ * log-likelihood with d/dt and d2/dt2, and the branch-length optimum
+ * (extension: RAxML's makenewz, next to plf() = newview and (7) = evaluate) --
+ * The CLVs MUST be in the eigen convention (PLFX_PMAT_EIGEN: P matrices from
+ * plfx_pmatrix, EV from plfx_model_ev, tips through plfx_model_tip_vectors).
+ * With V = Pi^-1/2 U (plfx_model_eigen) V^T Pi V = I, so for the CLVs a, b at
+ * the two ends of a branch of length t
+ *   L_i(t) = sum_c catw[c] * sum_k a[i][c][k] * b[i][c][k] * exp(lambda_k r_c t)
+ * with no further weights; a and b stay fixed while t varies.  STATE-
+ * convention CLVs give meaningless results (not detected).
+ *
+ * Sum table: sumtab[i][c][k] = x1[i][c][k] * x2[i][c][k], one multiply
+ * rounded in dtype; the layout is the CLV layout (n * 4 * states values),
+ * states 4 or 20.  Side 1 is either dense (x1) or a coded tip (tip1: uint8
+ * codes as in section 8, then x1[i][c][k] = tipvec[row][k] with row =
+ * code & 15 of 16 x 4 for DNA and min(code, 23) of 24 x 20 for protein);
+ * exactly one of tip1 / x1 is non-NULL and tipvec is required with tip1 (the
+ * default 0/1 table is not in eigen coordinates).  Only side 1 may be coded:
+ * the product is symmetric, so pass the tip first.  x1, x2, sumtab: 16-byte
+ * aligned; sumtab may not share a byte with x1 or x2.  f32 products of two
+ * very small entries may underflow (as RAxML's f32 sum table would): the
+ * table is not rescaled.  Asynchronous, capture-safe. */
+int plfx_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                       const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream);
+
+/* out3 (3 device doubles), all arithmetic in f64, with x_ck = lambda_k r_c,
+ * e = exp(x t), e1 = e x, e2 = e1 x and L, L1, L2 = sum_c catw[c] sum_k
+ * sumtab[i][c][k] * {e, e1, e2} (ascending k, then ascending c):
+ *   out3[0] = sum_i wgt_i log L_i + (sum_{j<nsums} scaler_sums[j]) * log(2^-32)
+ *   out3[1] = sum_i wgt_i L1/L                   (d lnL / dt)
+ *   out3[2] = sum_i wgt_i (L2/L - (L1/L)^2)      (d2 lnL / dt2)
+ * Scaling cancels in out3[1], out3[2].  eigen: the device array plfx_pmatrix
+ * takes (only lambda is read); rates: device, ncat doubles; ncat must be 4
+ * (PLFX_ERR_UNSUPPORTED otherwise); t: one device double; catw, wgt,
+ * scaler_sums as in plfx_root_lnl (NULL: uniform, 1, none); site_lnl:
+ * optional device double[n], log L_i.  n == 0: out3 = {correction, 0, 0}.
+ * Deterministic (the fixed reduction order of (7)); asynchronous, uses the
+ * stream's workspace, capture-safe as plfx_root_lnl. */
+int plfx_edge_derivatives(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                          const double *eigen, const double *rates, int ncat, const double *catw,
+                          const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                          double *out3, double *site_lnl, void *stream);
+
+/* The branch length in [tmin, tmax] that maximises the edge log-likelihood: a
+ * bracketed Newton iteration on d lnL/dt from t0.  After each evaluation
+ * d1 > 0 raises the lower end of the bracket to t, else the upper end drops
+ * to t; the next t is the Newton step t - d1/d2 when d2 < 0 and the step
+ * lands strictly inside the bracket, else the geometric mean of the bracket's
+ * ends; it stops when the step is <= 1e-10 t, the bracket's ends are within
+ * 1 + 1e-10 of each other, or after max_evals evaluations.  When d1 has one
+ * sign on the whole interval the result is tmin or tmax itself.  Host-
+ * synchronous (24 bytes come back per evaluation through a buffer of the
+ * context; nothing is allocated): PLFX_ERR_INVALID on a capturing stream and
+ * unless 0 < tmin <= t0 <= tmax, max_evals >= 1.  t_opt, out3_host (may be
+ * NULL; lnL without scaling correction, d1, d2 at t_opt) and evals (may be
+ * NULL; evaluations made) are host pointers; the rest as above. */
+int plfx_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                       const double *eigen, const double *rates, int ncat, const double *catw,
+                       const int32_t *wgt, double t0, double tmin, double tmax, int max_evals,
+                       double *t_opt, double *out3_host, int *evals, void *stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
