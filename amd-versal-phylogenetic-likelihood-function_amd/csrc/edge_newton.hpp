@@ -15,28 +15,33 @@
 // sign on all of [tmin, tmax]: the optimum is that end) gets one last
 // evaluation at the end itself, so the result is tmin or tmax exactly and the
 // last evaluation is always the result's.
+//
+// The arithmetic is EdgeNewtonStep's (edge_newton_step.hpp), which the device
+// loop of plfx_edge_optimize_dev shares; this class adds the argument check
+// and the evaluation cap.
 #pragma once
+#include "edge_newton_step.hpp"
 
 namespace plfx {
 
 class EdgeNewton {
  public:
-  static constexpr double kTol = 1e-10;
+  static constexpr double kTol = EdgeNewtonStep::kTol;
   // requires 0 < tmin <= t0 <= tmax, max_evals >= 1 (valid() otherwise false)
   EdgeNewton(double t0, double tmin, double tmax, int max_evals);
   bool valid() const { return valid_; }
   // where to evaluate next; after the last advance(), the result
-  double t() const { return t_; }
+  double t() const { return s_.t; }
   // the derivatives at t(): true = evaluate again at the new t()
   bool advance(double d1, double d2);
-  int evals() const { return evals_; }
-  double lo() const { return lo_; }
-  double hi() const { return hi_; }
+  int evals() const { return s_.evals; }
+  double lo() const { return s_.lo; }
+  double hi() const { return s_.hi; }
 
  private:
-  double t_, lo_, hi_;
-  int max_evals_, evals_ = 0;
-  bool lo_seen_ = false, hi_seen_ = false, last_ = false, valid_;
+  EdgeNewtonStep s_;
+  int max_evals_;
+  bool valid_;
 };
 
 }  // namespace plfx

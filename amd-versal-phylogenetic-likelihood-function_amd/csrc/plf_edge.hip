@@ -39,24 +39,55 @@ hipError_t launch_edge_sumtable_t(const void *x1, const void *x2, int64_t n, con
 
 // Edge derivatives: the grids of the root-lnL kernels they are modelled on
 // (launch_lnl_t, launch_lnl_prot_t), under the context's grid cap.
+// (edge_deriv_grid: also the one-edge grid of the device loop below, whose
+// sums then have the derivative kernels' slots and order.)
 template <typename T>
-hipError_t launch_edge_deriv_t(int states, const T *st, int64_t n, const double *lambda, const double *rates,
-                               const double *catw, const int32_t *wgt, const double *t, const int64_t *sums,
-                               int nsums, double *partials, unsigned long long *ticket, double *out,
-                               double *site_lnl, int max_blocks, hipStream_t s) {
+int64_t edge_deriv_grid(int states, int64_t n, int max_blocks) {
   static int cache4 = 0, cache20 = 0;
   if (states == 4) {
     auto kernel = &dev::edge_deriv_kernel<T, 4, 4>;
     int64_t gx = grid_x((const void *)kernel, cache4, n, kWavesPerBlock * 64, 1, max_blocks);
     if (max_blocks <= 0) gx = std::min<int64_t>(gx, 2 * (int64_t)cu_count());
-    gx = std::min<int64_t>(gx, kLnlMaxGrid);
-    return launch(kernel, dim3((unsigned)gx), kBlock, s, st, n, lambda, rates, catw, wgt, t, sums, nsums,
-                  partials, ticket, out, site_lnl);
+    return std::min<int64_t>(gx, kLnlMaxGrid);
   }
   auto kernel = &dev::edge_deriv_prot_kernel<T>;
-  const int64_t gx = std::min<int64_t>(grid_x((const void *)kernel, cache20, n, 64, 1, max_blocks), kLnlMaxGrid);
-  return launch(kernel, dim3((unsigned)gx), kBlock, s, st, n, lambda, rates, catw, wgt, t, sums, nsums,
-                partials, ticket, out, site_lnl);
+  return std::min<int64_t>(grid_x((const void *)kernel, cache20, n, 64, 1, max_blocks), kLnlMaxGrid);
+}
+
+template <typename T>
+hipError_t launch_edge_deriv_t(int states, const T *st, int64_t n, const double *lambda, const double *rates,
+                               const double *catw, const int32_t *wgt, const double *t, const int64_t *sums,
+                               int nsums, double *partials, unsigned long long *ticket, double *out,
+                               double *site_lnl, int max_blocks, hipStream_t s) {
+  const int64_t gx = edge_deriv_grid<T>(states, n, max_blocks);
+  if (states == 4)
+    return launch(&dev::edge_deriv_kernel<T, 4, 4>, dim3((unsigned)gx), kBlock, s, st, n, lambda, rates, catw,
+                  wgt, t, sums, nsums, partials, ticket, out, site_lnl);
+  return launch(&dev::edge_deriv_prot_kernel<T>, dim3((unsigned)gx), kBlock, s, st, n, lambda, rates, catw, wgt,
+                t, sums, nsums, partials, ticket, out, site_lnl);
+}
+
+// The device loop: max_evals launches of edge_opt_kernel over the group's
+// edges (blockIdx.y); the first of them initialises the per-edge state.  The
+// per-edge grid is the one-edge grid unless the group's 3 * gx * count slots
+// would not fit the 3 * kLnlMaxGrid doubles of `partials`.
+template <typename T, int S>
+hipError_t launch_edge_opt_t(const void *const *tabs, int count, int64_t n, const double *lambda,
+                             const double *rates, const double *catw, const int32_t *wgt, const double *t0,
+                             double tmin, double tmax, int max_evals, void *state, double *partials,
+                             unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
+                             int max_blocks, hipStream_t s) {
+  static_assert(dev::kMaxBatch == kMaxBatch && dev::kWsWords == kWsWords, "batch constants");
+  dev::EdgeOptTabs a{};
+  for (int j = 0; j < count; j++) a.st[j] = tabs[j];
+  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(edge_deriv_grid<T>(S, n, max_blocks), kLnlMaxGrid / count));
+  for (int i = 0; i < max_evals; i++) {
+    hipError_t e = launch(&dev::edge_opt_kernel<T, S>, dim3((unsigned)gx, (unsigned)count), kBlock, s, a, n, lambda,
+                          rates, catw, wgt, t0, tmin, tmax, max_evals, (int)(i == 0),
+                          static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3, evals);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace
@@ -83,6 +114,21 @@ hipError_t launch_edge_derivatives(int dtype, int states, const void *sumtab, in
                                       nsums, partials, ticket, out3, site_lnl, max_blocks, s);
       },
       bools{dtype == 1});
+}
+
+hipError_t launch_edge_optimize(int dtype, int states, const void *const *sumtabs, int count, int64_t n,
+                                const double *lambda, const double *rates, const double *catw,
+                                const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                                void *state, double *partials, unsigned long long *ws, double *t_opt,
+                                double *out3, int32_t *evals, int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto kStates, auto k64) {
+        return launch_edge_opt_t<real_t<k64()>, kStates()>(sumtabs, count, n, lambda, rates, catw, wgt, t0, tmin,
+                                                           tmax, max_evals, state, partials, ws, t_opt, out3,
+                                                           evals, max_blocks, s);
+      },
+      among<4, 20>{states}, bools{dtype == 1});
 }
 
 }  // namespace plfx

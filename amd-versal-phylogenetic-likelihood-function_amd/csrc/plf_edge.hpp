@@ -16,10 +16,13 @@
 //   out[2] = sum_i w_i (L2/L - (L1/L)^2)     = d2 lnL / dt2
 // Scaling multiplies L, L1 and L2 of a site alike, so it cancels in out[1],
 // out[2].  The three sums share plf_lnl.hpp's fixed-order reduction (N = 3).
+// At the end of the file: the branch-length iteration over these sums with the
+// loop on the device (edge_opt_kernel, plfx_edge_optimize_dev).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "edge_newton_step.hpp"
 #include "plf_lnl.hpp"
 
 namespace plfx {
@@ -109,14 +112,18 @@ __device__ __forceinline__ double quad_cat_sum(const double (&cw)[4], double t) 
 
 // S = 4: root_lnl_kernel's arrangement (C lanes per site, lane = category,
 // lane c takes the log and the two quotients of step c's site).  A lane's
-// table is its category's 3 x S factors, in registers.
+// table is its category's 3 x S factors, in registers.  The block's share of
+// the sites into acc, at branch length t: the body of edge_deriv_kernel and
+// of edge_opt_kernel (blocks along x).  partials: only a readable word here
+// (wgt_at's dummy).
 template <typename T, int S, int C>
-__global__ void __launch_bounds__(kBlock)
-edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
-                  const double *__restrict__ rates, const double *__restrict__ catw,
-                  const int32_t *__restrict__ wgt, const double *__restrict__ tp,
-                  const int64_t *__restrict__ scaler_sums, int nsums, double *partials,
-                  unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+__device__ __forceinline__ void edge_deriv_sites(const T *__restrict__ st, int64_t n,
+                                                 const double *__restrict__ lambda,
+                                                 const double *__restrict__ rates,
+                                                 const double *__restrict__ catw,
+                                                 const int32_t *__restrict__ wgt, const double t,
+                                                 const double *partials, double *__restrict__ site_lnl,
+                                                 double (&acc)[3]) {
   static_assert(C == 4, "a site's categories are the lanes of a quad (quad_cat_sum)");
   constexpr int V = S * C;
   constexpr int SPW = 64 / C;  // sites per wave step
@@ -125,7 +132,7 @@ edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict_
   const int q = lane / C;
   double e0[S], e1[S], e2[S];
   {
-    const double t = *tp, r = rates[c];
+    const double r = rates[c];
 #pragma unroll
     for (int k = 0; k < S; k++) edge_factors(lambda[k], r, t, e0[k], e1[k], e2[k]);
   }
@@ -133,7 +140,6 @@ edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict_
 #pragma unroll
   for (int k = 0; k < C; k++) cw[k] = catw ? catw[k] : 1.0 / C;
 
-  double acc[3] = {0.0, 0.0, 0.0};
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * SPW * C;
   const int64_t nlast = n - 1;
@@ -186,6 +192,17 @@ edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict_
       if (site_lnl) site_lnl[site] = l;
     }
   }
+}
+
+template <typename T, int S, int C>
+__global__ void __launch_bounds__(kBlock)
+edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
+                  const double *__restrict__ rates, const double *__restrict__ catw,
+                  const int32_t *__restrict__ wgt, const double *__restrict__ tp,
+                  const int64_t *__restrict__ scaler_sums, int nsums, double *partials,
+                  unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  edge_deriv_sites<T, S, C>(st, n, lambda, rates, catw, wgt, *tp, partials, site_lnl, acc);
   lnl_finish<3>(acc, partials, ticket, out, scaler_sums, nsums);
 }
 
@@ -197,12 +214,13 @@ edge_deriv_kernel(const T *__restrict__ st, int64_t n, const double *__restrict_
 // and left one block per CU).  The category sums meet in LDS and wave 0 forms
 // L, L1, L2 and the site's terms.
 template <typename T>
-__global__ void __launch_bounds__(kBlock)
-edge_deriv_prot_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
-                       const double *__restrict__ rates, const double *__restrict__ catw,
-                       const int32_t *__restrict__ wgt, const double *__restrict__ tp,
-                       const int64_t *scaler_sums, int nsums, double *partials,
-                       unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+__device__ __forceinline__ void edge_deriv_prot_sites(const T *__restrict__ st, int64_t n,
+                                                      const double *__restrict__ lambda,
+                                                      const double *__restrict__ rates,
+                                                      const double *__restrict__ catw,
+                                                      const int32_t *__restrict__ wgt, const double t,
+                                                      const double *partials, double *__restrict__ site_lnl,
+                                                      double (&acc)[3]) {
   constexpr int S = 20, C = 4;
   using PT = ProtTile<T>;
   constexpr int K = PT::kChunks / kBlock;
@@ -212,7 +230,7 @@ edge_deriv_prot_kernel(const T *__restrict__ st, int64_t n, const double *__rest
   if (threadIdx.x < C * S) {
     const int tc_ = threadIdx.x / S, tk = threadIdx.x % S;
     double a0, a1, a2;
-    edge_factors(lambda[tk], rates[tc_], *tp, a0, a1, a2);
+    edge_factors(lambda[tk], rates[tc_], t, a0, a1, a2);
     tab[0][tc_][tk] = a0;
     tab[1][tc_][tk] = a1;
     tab[2][tc_][tk] = a2;
@@ -225,7 +243,6 @@ edge_deriv_prot_kernel(const T *__restrict__ st, int64_t n, const double *__rest
   const int64_t stride = (int64_t)gridDim.x * 64;
   typename PT::V pf[K];
   if ((int64_t)blockIdx.x * 64 < n) tile_fetch<T>(st, (int64_t)blockIdx.x * 64, n, pf);
-  double acc[3] = {0.0, 0.0, 0.0};
   for (int64_t base = (int64_t)blockIdx.x * 64; base < n; base += stride) {
     const int64_t site = base + lane;
     const bool valid = site < n;
@@ -260,7 +277,95 @@ edge_deriv_prot_kernel(const T *__restrict__ st, int64_t n, const double *__rest
     }
     __syncthreads();  // tc is rewritten by the next trip
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+edge_deriv_prot_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
+                       const double *__restrict__ rates, const double *__restrict__ catw,
+                       const int32_t *__restrict__ wgt, const double *__restrict__ tp,
+                       const int64_t *scaler_sums, int nsums, double *partials,
+                       unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  edge_deriv_prot_sites<T>(st, n, lambda, rates, catw, wgt, *tp, partials, site_lnl, acc);
   lnl_finish<3>(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+// ---- the branch-length loop on the device (plfx_edge_optimize_dev) ----
+//
+// One launch = one evaluation of every edge of a group that has not stopped
+// (blockIdx.y = edge, gridDim.x blocks per edge) and, in the thread that holds
+// the edge's totals, one step of its bracket (edge_newton_step.hpp).  The host
+// enqueues max_evals such launches; nothing waits inside a launch.
+//
+// Per edge j: its state state[j] (the stepper struct, in the stream
+// workspace), its ticket words ws + j * kWsWords and its 3 * gridDim.x partial
+// slots.  The first launch of a call (first != 0) does not read the state: t
+// is t0[j] clamped into [tmin, tmax] and the electing thread initialises the
+// state before it steps, so a replayed graph needs no reset.  In later
+// launches every block reads the edge's flags and t at entry; the state was
+// written by an earlier launch of the same stream, so all blocks of the edge
+// agree, and a stopped edge's blocks return before they touch partials or
+// tickets.  Within a launch the state is written only after every block of the
+// edge has drawn its ticket, i.e. after every entry read.  The thread that
+// stops an edge writes t_opt[j], out3[3j..], evals[j] (the last two optional).
+struct EdgeOptTabs {
+  const void *st[kMaxBatch];
+};
+static_assert(sizeof(EdgeNewtonStep) == 32, "plf_kernels.hpp kEdgeStateBytes");
+
+__device__ __forceinline__ double edge_opt_entry(const EdgeNewtonStep *sp, const double *t0,
+                                                 double tmin, double tmax, int first, bool &done) {
+  const int j = blockIdx.y;
+  done = false;
+  if (first) {
+    const double t = t0[j];
+    return !(t >= tmin) ? tmin : (t > tmax ? tmax : t);  // a NaN starts at tmin
+  }
+  done = (__hip_atomic_load(&sp->flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & EdgeNewtonStep::kDone) != 0;
+  return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long *>(&sp->t),
+                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// the electing thread: acc holds the edge's lnL, d1, d2 at t
+__device__ __forceinline__ void edge_opt_step(EdgeNewtonStep *sp, const double (&acc)[3], double t, double tmin,
+                                              double tmax, int max_evals, int first, double *t_opt,
+                                              double *out3, int32_t *evals) {
+  const int j = blockIdx.y;
+  EdgeNewtonStep s;
+  if (first) s.init(t, tmin, tmax);
+  else s = *sp;
+  if (!s.advance(acc[1], acc[2], max_evals)) {
+    s.flags |= EdgeNewtonStep::kDone;
+    t_opt[j] = s.t;
+    if (out3) {
+      out3[3 * j] = acc[0];
+      out3[3 * j + 1] = acc[1];
+      out3[3 * j + 2] = acc[2];
+    }
+    if (evals) evals[j] = s.evals;
+  }
+  *sp = s;
+}
+
+template <typename T, int S>
+__global__ void __launch_bounds__(kBlock)
+edge_opt_kernel(const EdgeOptTabs tabs, int64_t n, const double *__restrict__ lambda,
+                const double *__restrict__ rates, const double *__restrict__ catw,
+                const int32_t *__restrict__ wgt, const double *t0, double tmin, double tmax,
+                int max_evals, int first, EdgeNewtonStep *state, double *partials, unsigned long long *ws,
+                double *t_opt, double *out3, int32_t *evals) {
+  EdgeNewtonStep *sp = state + blockIdx.y;
+  bool done;
+  const double t = edge_opt_entry(sp, t0, tmin, tmax, first, done);
+  if (done) return;
+  const T *st = static_cast<const T *>(tabs.st[blockIdx.y]);
+  double *part = partials + (size_t)blockIdx.y * 3 * gridDim.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  if constexpr (S == 4) edge_deriv_sites<T, 4, 4>(st, n, lambda, rates, catw, wgt, t, part, nullptr, acc);
+  else edge_deriv_prot_sites<T>(st, n, lambda, rates, catw, wgt, t, part, nullptr, acc);
+  if (lnl_finish<3, false>(acc, part, ws + (size_t)blockIdx.y * kWsWords, nullptr, nullptr, 0))
+    edge_opt_step(sp, acc, t, tmin, tmax, max_evals, first, t_opt, out3, evals);
 }
 
 }  // namespace dev

@@ -112,6 +112,20 @@ hipError_t launch_edge_derivatives(int dtype, int states, const void *sumtab, in
                                    unsigned long long *ticket, double *out3, double *site_lnl,
                                    int max_blocks, hipStream_t s);
 
+// The branch-length loop of plfx_edge_optimize_dev for count <= kMaxBatch
+// edges that share n, the model and wgt: max_evals launches, one evaluation
+// and one step of every unfinished edge each (plf_edge.hpp edge_opt_kernel).
+// sumtabs: host array of device tables; t0, t_opt (count), out3 (3 * count, may
+// be null), evals (count, may be null): device.  state: kMaxBatch *
+// kEdgeStateBytes bytes (no rest state: the first launch writes it); partials
+// as above; ws: kMaxBatch regions of kWsWords (zero at rest).
+constexpr int kEdgeStateBytes = 32;  // sizeof(EdgeNewtonStep), asserted in plf_edge.hpp
+hipError_t launch_edge_optimize(int dtype, int states, const void *const *sumtabs, int count, int64_t n,
+                                const double *lambda, const double *rates, const double *catw,
+                                const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                                void *state, double *partials, unsigned long long *ws, double *t_opt,
+                                double *out3, int32_t *evals, int max_blocks, hipStream_t s);
+
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,
                              hipStream_t s);

@@ -30,9 +30,12 @@ constexpr double kLogMinLik = -22.18070977791824990137;  // log(2^-32) = -32 ln 
 // edge derivatives (plf_edge.hpp, N = 3): the block's lanes' N accumulators
 // into fixed slots (accumulator j of block b at partials[j * gridDim.x + b]),
 // the last block (two-level election) sums each accumulator's slots in index
-// order; out[0] also gets the scaler correction.
-template <int N>
-__device__ __forceinline__ void lnl_finish(double (&acc)[N], double *partials, unsigned long long *ticket,
+// order; out[0] also gets the scaler correction.  Returns true in the one
+// thread that formed the totals (thread 0 of the last block), with them in
+// acc, so a caller may go on from there (plf_edge.hpp edge_opt_kernel steps
+// its bracket in that thread); kStore = false leaves out unwritten.
+template <int N, bool kStore = true>
+__device__ __forceinline__ bool lnl_finish(double (&acc)[N], double *partials, unsigned long long *ticket,
                                            double *out, const int64_t *__restrict__ scaler_sums, int nsums) {
   const int lane = threadIdx.x & 63;
   // fixed-order block reduction
@@ -75,7 +78,7 @@ __device__ __forceinline__ void lnl_finish(double (&acc)[N], double *partials, u
     last = is_last;
   }
   __syncthreads();
-  if (!last) return;
+  if (!last) return false;
   double v[N];
 #pragma unroll
   for (int j = 0; j < N; j++) {
@@ -101,10 +104,13 @@ __device__ __forceinline__ void lnl_finish(double (&acc)[N], double *partials, u
       double tot = 0.0;
 #pragma unroll
       for (int i = 0; i < kWavesPerBlock; i++) tot += part[j][i];
-      out[j] = j == 0 ? tot + (double)nsc * kLogMinLik : tot;
+      acc[j] = j == 0 ? tot + (double)nsc * kLogMinLik : tot;
+      if constexpr (kStore) out[j] = acc[j];
     }
     __hip_atomic_store(ticket + kSlots * 16, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
   }
+  return false;
 }
 
 // one accumulator: the root lnL

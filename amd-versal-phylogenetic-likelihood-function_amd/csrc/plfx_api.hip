@@ -93,6 +93,8 @@ constexpr size_t kWsBytes = kWsRegions * plfx::kWsWords * sizeof(unsigned long l
 constexpr size_t kLnlPartialBytes = 3 * (size_t)plfx::kLnlMaxGrid * sizeof(double);
 constexpr size_t kEdgeBufBytes = 4 * sizeof(double);
 constexpr size_t kLnlTicketBytes = plfx::kWsWords * sizeof(unsigned long long);
+// plfx_edge_optimize_dev: the stepper state of each edge of a launch group
+constexpr size_t kEdgeStateRegionBytes = (size_t)plfx::kMaxBatch * plfx::kEdgeStateBytes;
 
 int fail(plfx_ctx *ctx, int code, const char *fmt, ...) {
   if (ctx) {
@@ -127,7 +129,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // to run on the context's own stream.
 hipStream_t pick(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
 
-constexpr size_t kWsEntryBytes = kWsBytes + kLnlPartialBytes + kLnlTicketBytes;
+constexpr size_t kWsEntryBytes = kWsBytes + kLnlPartialBytes + kLnlTicketBytes + kEdgeStateRegionBytes;
 
 // Tip/tip protein combination tables (plf_prot.hpp prot_tiptip_gather_kernel):
 // per node of a launch group, a 576 x 80 table of the node's dtype and 576
@@ -176,6 +178,7 @@ void ws_carve(StreamWs &w, void *base, void *tt) {
   w.ws = reinterpret_cast<unsigned long long *>(b);
   w.lnl_partials = reinterpret_cast<double *>(b + kWsBytes);
   w.lnl_ticket = reinterpret_cast<unsigned long long *>(b + kWsBytes + kLnlPartialBytes);
+  w.edge_state = b + kWsBytes + kLnlPartialBytes + kLnlTicketBytes;
   w.tt = static_cast<char *>(tt);
 }
 
@@ -1261,6 +1264,36 @@ int plfx_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab,
   *t_opt = t;
   if (out3_host) std::copy(out, out + 3, out3_host);
   if (evals) *evals = step.evals();
+  return PLFX_OK;
+}
+
+int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
+                           int64_t n, const double *eigen, const double *rates, int ncat, const double *catw,
+                           const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                           double *t_opt, double *out3, int32_t *evals, void *stream) {
+  PLFX_BIND(ctx);
+  if (nedges < 1 || !sumtabs) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: nedges=%d / null sumtabs", nedges);
+  for (int j = 0; j < nedges; j++) {
+    if (!sumtabs[j]) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: sum table %d is null", j);
+    if (int rc = check_edge_args(ctx, dtype, states, sumtabs[j], n, eigen, rates, ncat); rc != PLFX_OK) return rc;
+  }
+  if (!t0 || !t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: null t0 / t_opt");
+  if (!(tmin > 0.0 && tmin <= tmax && std::isfinite(tmax)) || max_evals < 1 || max_evals > PLFX_EDGE_MAX_EVALS)
+    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: needs 0 < tmin <= tmax < inf and 1 <= max_evals <= %d",
+                PLFX_EDGE_MAX_EVALS);
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // groups of kMaxBatch edges, one after the other on the stream: a group's
+  // launches are done with the state, ticket and partial regions before the
+  // next group's first launch rewrites the state
+  for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
+    const int c = std::min(nedges - g, plfx::kMaxBatch);
+    hipError_t e = plfx::launch_edge_optimize(dtype, states, sumtabs + g, c, n, eigen, rates, catw, wgt, t0 + g, tmin,
+                                              tmax, max_evals, w->edge_state, w->lnl_partials, w->ws, t_opt + g,
+                                              out3 ? out3 + 3 * (size_t)g : nullptr, evals ? evals + g : nullptr,
+                                              ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_dev launch");
+  }
   return PLFX_OK;
 }
 

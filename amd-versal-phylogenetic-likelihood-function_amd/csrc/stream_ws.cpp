@@ -53,6 +53,7 @@ void WsPool::add(const StreamWs &w) {
   e.ws = w.ws;
   e.lnl_partials = w.lnl_partials;
   e.lnl_ticket = w.lnl_ticket;
+  e.edge_state = w.edge_state;
   e.tt = w.tt;
   wss_.push_back(e);
 }

@@ -19,6 +19,7 @@ class StreamWs {
   unsigned long long *ws = nullptr;  // kWsRegions x kWsWords u64
   double *lnl_partials = nullptr;    // 3 x kLnlMaxGrid doubles (plf_edge.hpp sums three values per block)
   unsigned long long *lnl_ticket = nullptr;
+  void *edge_state = nullptr;  // plfx_edge_optimize_dev: kMaxBatch per-edge stepper states (no rest state)
   // tip/tip protein combination tables (kTtEntryBytes): allocated with the
   // entry, or on first use with PLFX_CTX_LAZY_TABLES (nullptr until then)
   char *tt = nullptr;

@@ -53,8 +53,9 @@ EXPORTS = (
     "plfx_model_eigen", "plfx_gamma_rates", "plfx_model_ev", "plfx_model_root_weights",
     "plfx_pmatrix", "plfx_model_tip_vectors",
     "plfx_shard", "plfx_gen_hostmem", "plfx_swemu_instance_run", "plfx_traverse_schedule",
-    "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize",
+    "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize", "plfx_edge_optimize_dev",
 )
+EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 MAX_STREAMS = 64   # PLFX_MAX_STREAMS
 WS_POOL = 8        # PLFX_WS_POOL
 STREAMS_MAX = 8    # PLFX_STREAMS_MAX
@@ -166,6 +167,8 @@ def load():
     dbl = C.c_double
     L.plfx_edge_optimize.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32,
                                      dp, dp, C.POINTER(i32), vp]
+    L.plfx_edge_optimize_dev.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl,
+                                         i32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -708,6 +711,34 @@ class Context:
         self._check(self._L.plfx_edge_optimize(*args, float(t0), float(tmin), float(tmax), int(max_evals),
                                                C.byref(t), out, C.byref(ev), self._sh(stream)))
         return t.value, out[0], out[1], out[2], ev.value
+
+    def optimize_branches(self, sumtabs, n, eigen, rates, t0, t_opt, tmin=1e-8, tmax=10.0, max_evals=64,
+                          out3=None, evals=None, catw=None, wgt=None, states=4, stream=None):
+        """optimize_branch for the independent branches whose sum tables are the
+        device tensors in `sumtabs`, with the loop on the device
+        (plfx_edge_optimize_dev): asynchronous, no synchronisation, capture-
+        safe.  t0, t_opt: float64 device tensors of len(sumtabs) (t0 is read
+        on the device: another call's t_opt may be passed); out3 (3 per
+        branch, float64) and evals (int32) are optional device tensors."""
+        import torch
+
+        m = len(sumtabs)
+        if m < 1:
+            raise PlfxError(ERR_INVALID, "sumtabs must hold at least one sum table")
+        for st in sumtabs:
+            if st.dtype != sumtabs[0].dtype:
+                raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
+            args = self._edge_args(st, n, eigen, rates, catw, wgt, states)
+        for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
+                              ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
+            if x is not None and (x.dtype != dt or x.numel() < cnt or not x.is_cuda or not x.is_contiguous()):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor of >= {cnt}")
+        if t0 is None or t_opt is None:
+            raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
+        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
+        tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
+        self._check(self._L.plfx_edge_optimize_dev(*args[:3], tabs, m, *args[4:], p(t0), float(tmin), float(tmax),
+                                                   int(max_evals), p(t_opt), p(out3), p(evals), self._sh(stream)))
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):

@@ -552,6 +552,37 @@ int plfx_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab,
                        const int32_t *wgt, double t0, double tmin, double tmax, int max_evals,
                        double *t_opt, double *out3_host, int *evals, void *stream);
 
+/* The same iteration for nedges independent branches with the loop kept on
+ * the device: asynchronous, allocates nothing, legal on a capturing stream
+ * (the stream's workspace, as plfx_root_lnl; so a stream's first use may be
+ * the capture while pool entries last).  sumtabs: HOST array of nedges device
+ * sum tables (n * 4 * states values of dtype each, 16-byte aligned, none
+ * NULL; the pointers travel in kernel arguments, as plfx_node's do, so the
+ * array may be reused after the call); n, eigen, rates, catw and wgt are
+ * shared by all edges.  t0: device, nedges doubles, read by the call's first
+ * launch -- so an earlier call's t_opt can be the next call's t0 with no host
+ * in between; a t0[j] outside [tmin, tmax] is clamped into it (the host
+ * cannot check it).  t_opt: device, nedges doubles.  out3: device, 3 * nedges
+ * doubles or NULL: edge j's lnL (no scaling correction), d1, d2 at t_opt[j].
+ * evals: device int32[nedges] or NULL: evaluations made.  Every edge walks
+ * the t sequence plfx_edge_optimize walks from the same start, bit for bit
+ * (one stepper, correctly rounded f64 arithmetic on both sides), and a
+ * one-edge call sums in plfx_edge_derivatives' order, so its t_opt, out3 and
+ * evals are plfx_edge_optimize's.  Deterministic.
+ * Mechanism: exactly max_evals launches per group of up to 32 edges, each one
+ * evaluation and one step of every edge of the group that has not stopped (a
+ * stopped edge's blocks return at entry); no grid-wide barrier.  max_evals
+ * therefore bounds the launches as well as the evaluations:
+ * PLFX_ERR_INVALID unless 1 <= max_evals <= PLFX_EDGE_MAX_EVALS, 0 < tmin <=
+ * tmax < infinity, nedges >= 1, t0 and t_opt non-NULL and every table
+ * non-NULL and aligned; PLFX_ERR_UNSUPPORTED as plfx_edge_derivatives. */
+#define PLFX_EDGE_MAX_EVALS 256
+int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
+                           int64_t n, const double *eigen, const double *rates, int ncat,
+                           const double *catw, const int32_t *wgt, const double *t0, double tmin,
+                           double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
+                           void *stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

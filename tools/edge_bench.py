@@ -13,6 +13,19 @@
 # the 8 TB/s HBM peak.
 #
 #   python tools/edge_bench.py [--calls 200] [--rounds 7]
+#
+# --optimize adds the time per branch-length optimisation, f64, of the host
+# loop (plfx_edge_optimize: one call per edge, a host wait per evaluation), of
+# the device loop (plfx_edge_optimize_dev: one call for all edges) issued
+# eagerly, and of the device loop as a replayed graph -- for 1 and 32 edges,
+# max_evals 64 and 16, at 10^4 and 2^20 DNA sites and 2^18 protein sites.  The
+# edges are two-taxon alignments simulated at distances between 0.05 and 1
+# (sampled on the device from a seed), every path starts every edge at t0 = 0.1,
+# and the evaluations each path made are recorded: the device loop enqueues
+# max_evals launches whatever it needs, the host loop stops when it converges.
+# These are host-clock times around work that ends in a synchronisation (the
+# host loop cannot be timed any other way), the three paths alternating within
+# every round, the median over the rounds after a warm-up round.
 import argparse
 import statistics
 import sys
@@ -28,10 +41,90 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, as bench.py
 GRAPH_CALLS = 20
 
 
+def simulated_tables(S, n, nedges, e, rates, seed):
+    """Sum tables (f64, device) of `nedges` two-taxon alignments under the
+    model `e` (plfx.model_eigen's array): one-hot ends in eigen coordinates,
+    the second end evolved from the first over a distance between 0.05 and 1."""
+    lam, Vm, Vi = e[:S], e[S:S + S * S].reshape(S, S), e[S + S * S:].reshape(S, S)
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    Vit = torch.from_numpy(np.ascontiguousarray(Vi.T)).cuda()  # row s: the eigen coordinates of state s
+    tables = []
+    for j in range(nedges):
+        tstar = float(np.geomspace(0.05, 1.0, max(nedges, 2))[j])
+        P = np.stack([np.clip((Vm * np.exp(lam * r * tstar)) @ Vi, 0, None) for r in rates])  # (4, S, S)
+        Pt = torch.from_numpy(P / P.sum(axis=2, keepdims=True)).cuda()
+        sa = torch.randint(0, S, (n,), device="cuda", generator=gen)
+        cat = torch.randint(0, 4, (n,), device="cuda", generator=gen)
+        sb = torch.multinomial(Pt[cat, sa], 1, generator=gen).squeeze(1)
+        st = (Vit[sa] * Vit[sb])[:, None, :].expand(n, 4, S).contiguous().reshape(-1)
+        tables.append(st)
+    return tables
+
+
+def optimize_rows(ctx, S, n, rounds):
+    import time
+
+    rng = np.random.default_rng(S)
+    exch, freqs = rng.random(S * (S - 1) // 2) + 0.5, rng.random(S) + 0.5
+    e = plfx.model_eigen(exch, freqs)
+    rates_np = plfx.gamma_rates(0.7, 4)
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()  # noqa: E731
+    eig, rates = dev(e), dev(rates_np)
+    wgt = torch.ones(n, dtype=torch.int32, device="cuda")
+    all_tables = simulated_tables(S, n, 32, e, rates_np, seed=S)
+    for nedges in (1, 32):
+        tables = all_tables[:nedges] if nedges > 1 else all_tables[15:16]
+        t0 = torch.full((nedges,), 0.1, dtype=torch.float64, device="cuda")
+        t_opt = torch.zeros(nedges, dtype=torch.float64, device="cuda")
+        evals = torch.zeros(nedges, dtype=torch.int32, device="cuda")
+        for max_evals in (64, 16):
+            side = torch.cuda.Stream()
+            host_evals = []
+
+            def host():
+                host_evals.clear()
+                for st in tables:
+                    host_evals.append(ctx.optimize_branch(st, n, eig, rates, 0.1, 1e-8, 10.0, max_evals, wgt=wgt,
+                                                          states=S, stream=side)[4])
+
+            def device():
+                ctx.optimize_branches(tables, n, eig, rates, t0, t_opt, 1e-8, 10.0, max_evals, evals=evals, wgt=wgt,
+                                      states=S, stream=side)
+
+            device()  # the stream's workspace, outside the capture
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                device()
+            paths = {"host loop": host, "device loop, eager": device, "device loop, graph": g.replay}
+            reps = 100 if n <= 100000 else 5
+            us = {k: [] for k in paths}
+            for rnd in range(rounds + 1):  # round 0 warms up
+                for name, fn in paths.items():
+                    torch.cuda.synchronize()
+                    b = time.perf_counter()
+                    for _ in range(reps):
+                        fn()
+                    torch.cuda.synchronize()
+                    if rnd:
+                        us[name].append((time.perf_counter() - b) * 1e6 / reps)
+            dev_evals = evals.cpu().numpy()
+            for name in paths:
+                med = statistics.median(us[name])
+                ev = host_evals if name == "host loop" else dev_evals.tolist()
+                print(f"S={S} f64 n={n} optimise edges={nedges:2d} max_evals={max_evals} {name:19s} {med:10.1f} us "
+                      f"(min {min(us[name]):.1f} max {max(us[name]):.1f}) {med / nedges:9.1f} us/edge "
+                      f"evals used mean {np.mean(ev):.1f} max {max(ev)}", flush=True)
+            del g
+            torch.cuda.synchronize()
+            ctx.release_stream(side)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--optimize", action="store_true", help="add the optimisation rows (see the head of this file)")
     ap.add_argument("--sites", type=int, nargs=2, default=[1 << 20, 1 << 18], metavar=("DNA", "PROTEIN"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -88,6 +181,9 @@ def main():
                   f"{n / med:8.1f} sites/us {gbs:7.1f} GB/s {gbs / HBM_PEAK_GBS:.3f} of HBM peak", flush=True)
         del graphs
         torch.cuda.synchronize()
+    if a.optimize:
+        for S, n in ((4, 10**4), (4, a.sites[0]), (20, a.sites[1])):
+            optimize_rows(ctx, S, n, a.rounds)
     ctx.close()
 
 
