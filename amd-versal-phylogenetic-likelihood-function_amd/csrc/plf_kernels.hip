@@ -371,8 +371,8 @@ hipError_t launch_plf_prot_batch(int dtype, bool fma, const NodeDescH *nodes, in
   const auto p = pack<dev::NodeBatch>(nodes, count, node_sum);
   return dispatch(
       [&](auto k64, auto kFma, auto kSum, auto kTips) {
-        // tips == 2 runs only as the combination tables of tip/tip nodes (plfx_api
-        // batch_impl), which carry no sum: a tip/tip node's sum comes from the
+        // tips == 2 runs only as the combination tables of tip/tip nodes (trav_lower.hpp
+        // kLaunchProtTipTip), which carry no sum: a tip/tip node's sum comes from the
         // gather, so the summing tip/tip forms are not built
         if constexpr (kTips() == 2 && kSum()) return hipErrorInvalidValue;
         else

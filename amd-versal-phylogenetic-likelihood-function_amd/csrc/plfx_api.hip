@@ -21,6 +21,7 @@
 #include "plf_kernels.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
+#include "trav_lower.hpp"
 #include "trav_plan.hpp"
 
 constexpr int kHostChunksMax = 16;
@@ -34,6 +35,9 @@ constexpr int kHostChunksMax = 16;
 // in: HIP rejects waiting on an event whose stream was destroyed -- an exited
 // thread's hipStreamPerThread gave hipErrorCapturedEvent (907) on the box.)
 using plfx::StreamWs;
+using plfx::aligned16;
+using plfx::clv_bytes_of;
+using plfx::overlap;
 constexpr int kWsPool = PLFX_WS_POOL;
 
 struct plfx_ctx {
@@ -51,6 +55,7 @@ struct plfx_ctx {
   uint8_t *tt_codes = nullptr;      // the tip/tip tables' two constant 576-code arrays (kTtCodeBytes)
   double *edge_buf = nullptr;       // plfx_edge_optimize: the trial t and the three results (kEdgeBufBytes)
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
+  plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -123,8 +128,6 @@ int check_dtype(plfx_ctx *ctx, int dtype) {
   return PLFX_OK;
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // NULL is the HIP null stream, as in every HIP API; pass plfx_ctx_stream(ctx)
 // to run on the context's own stream.
 hipStream_t pick(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
@@ -141,9 +144,7 @@ constexpr size_t kWsEntryBytes = kWsBytes + kLnlPartialBytes + kLnlTicketBytes +
 // call instead, and that first call is refused (PLFX_ERR_INVALID) inside a
 // capture.
 constexpr size_t kTtCodeBytes = 2048;
-constexpr size_t kTtTabBytes = (size_t)plfx::kProtCombos * 80 * sizeof(double);
-constexpr size_t kTtScBytes = 1024;
-constexpr size_t kTtEntryBytes = (size_t)plfx::kMaxBatch * (kTtTabBytes + kTtScBytes);
+constexpr size_t kTtEntryBytes = (size_t)plfx::kMaxBatch * (plfx::kTtTabBytes + plfx::kTtScBytes);
 
 bool capturing(hipStream_t s) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -253,12 +254,6 @@ StreamWs *ws_for(plfx_ctx *ctx, hipStream_t s, int *rc) {
     out = ws_for((ctx), (s), &wrc_);              \
     if (!out) return wrc_;                        \
   } while (0)
-
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return na > 0 && nb > 0 && pa < pb + nb && pb < pa + na;
-}
 
 // clv_bytes: bytes of one CLV of the call (n * 4 categories * states * element
 // size); a tip child is n code bytes.  The parent may not share a byte with
@@ -395,88 +390,8 @@ int plf_host(plfx_ctx *ctx, const T *x1, const T *x2, T *x3, const T *EV, int n,
   return PLFX_OK;
 }
 
-// One node of a kind (tips = number of tip children, tip child first); i
-// names it in the message (the op index in a traversal); clv_bytes as
-// check_dev_args.
-int check_node(plfx_ctx *ctx, const plfx_node &d, int tips, int64_t n, int i, size_t clv_bytes) {
-  if (n <= 0) return PLFX_OK;
-  if (!d.x1 || !d.x2 || !d.x3 || !d.left || !d.right)
-    return fail(ctx, PLFX_ERR_INVALID, "node %d: null CLV/tip/matrix pointer", i);
-  if ((tips < 1 && !aligned16(d.x1)) || (tips < 2 && !aligned16(d.x2)) || !aligned16(d.x3))
-    return fail(ctx, PLFX_ERR_INVALID, "node %d: CLV pointers must be 16-byte aligned", i);
-  const size_t b1 = tips >= 1 ? (size_t)n : clv_bytes, b2 = tips >= 2 ? (size_t)n : clv_bytes;
-  if (overlap(d.x3, clv_bytes, d.x1, b1) || overlap(d.x3, clv_bytes, d.x2, b2))
-    return fail(ctx, PLFX_ERR_INVALID, "node %d: x3 may not overlap a child", i);
-  return PLFX_OK;
-}
-
-size_t clv_bytes_of(int dtype, int states, int64_t n) {
-  return (size_t)(n > 0 ? n : 0) * 4 * states * (dtype == PLFX_F32 ? 4 : 8);
-}
-
-// The arrays of a traversal call (plfx_traverse_tips): its ops as node descriptors.
-struct TravNodes {
-  const plfx_trav_op *ops;
-  void *const *clv;
-  const uint8_t *const *tips;  // may be NULL
-  const char *pmats;
-  size_t mat_bytes;  // of one matrix (C*S*S values)
-  uint8_t *const *scalers;
-  int64_t *scaler_sums;
-  // the node descriptor of op j, tip child first (dense/tip runs as tip/dense:
-  // the product u1*u2 commutes exactly); *kind = number of tip children
-  plfx_node node(int j, int *kind) const {
-    const plfx_trav_op &o = ops[j];
-    const bool t1 = tips && tips[o.child1], t2 = tips && tips[o.child2];
-    plfx_node nd{t1 ? (const void *)tips[o.child1] : clv[o.child1],
-                 t2 ? (const void *)tips[o.child2] : clv[o.child2], clv[o.parent],
-                 pmats + (size_t)(2 * o.pmat) * mat_bytes, pmats + (size_t)(2 * o.pmat + 1) * mat_bytes,
-                 scalers ? scalers[j] : nullptr, scaler_sums ? scaler_sums + j : nullptr};
-    if (!t1 && t2) {
-      std::swap(nd.x1, nd.x2);
-      std::swap(nd.left, nd.right);
-    }
-    *kind = (t1 ? 1 : 0) + (t2 ? 1 : 0);
-    return nd;
-  }
-};
-
-// The descriptor of a fused pass (DeepDescH, SeptetDescH) over the ops ids[0..count),
-// each checked as a node; the first `leaves` of them are the leaf ops, whose
-// children are the pass's inputs g.  A septet's leaf ops come tip child first
-// (node()); a deep pass's leaves are all dense or all tips, so there child1,
-// child2 stay as the op names them.
-template <typename Desc>
-int fill_fused(plfx_ctx *ctx, const TravNodes &tn, const int *ids, int count, int leaves, int64_t n,
-               size_t clv_bytes, Desc *d) {
-  for (int q = 0; q < count; q++) {
-    int kq;
-    const plfx_node nd = tn.node(ids[q], &kq);
-    const int rc = check_node(ctx, nd, kq, n, ids[q], clv_bytes);
-    if (rc != PLFX_OK) return rc;
-    if (q < leaves) {
-      d->g[2 * q] = nd.x1;
-      d->g[2 * q + 1] = nd.x2;
-    }
-    d->x[q] = nd.x3;
-    d->mat[2 * q] = nd.left;
-    d->mat[2 * q + 1] = nd.right;
-    d->sc[q] = nd.scaler;
-    d->ss[q] = nd.scaler_sum;
-  }
-  return PLFX_OK;
-}
-
-// A tip/tip protein node whose values sit in its stream's combination tables
-// after batch_impl: its CLV (x3), its table and its two tip-code arrays.
-struct TabRef {
-  const void *x3;
-  const void *tab;
-  const uint8_t *ca, *cb;
-};
-
-// What the batches of one call share: the entry point's arguments.
-struct BatchCall {
+// What the launches of one call share: the entry point's arguments.
+struct ExecCall {
   int dtype, states, flags;
   const void *EV;
   int64_t n;
@@ -486,123 +401,101 @@ struct BatchCall {
   int streams;  // DNA batches share the resident grid with the batches of this many streams in flight
 };
 
-// Nodes of one kind (tips = number of tip children, tip child first) in
-// launches of kMaxBatch.  A tip child is a uint8 code array (no alignment rule).
-// ids (may be NULL) names the nodes in messages (the op indices in a
-// traversal).  *launches counts the kernel launches issued (may be NULL).
-// *tabs (may be NULL) receives the tip/tip protein nodes whose tables are
-// still in the stream's workspace afterwards (the last launch group's).
-int batch_impl(plfx_ctx *ctx, const BatchCall &call, const plfx_node *nodes, int count, int tips,
-               const int *ids = nullptr, int *launches = nullptr, std::vector<TabRef> *tabs = nullptr) {
-  const int dtype = call.dtype, states = call.states;
-  const bool fma = (call.flags & PLFX_FMA) != 0;
-  const void *EV = call.EV, *tipvec = call.tipvec;
-  const int64_t n = call.n;
-  const int32_t *wgt = call.wgt;
-  hipStream_t s = call.s;
-  if (tabs) tabs->clear();
-  if (count < 0 || n < 0 || (count > 0 && (!nodes || !EV)))
-    return fail(ctx, PLFX_ERR_INVALID, "bad batch arguments");
-  for (int i = 0; i < count; i++) {
-    const plfx_node &d = nodes[i];
-    int rc = check_node(ctx, d, tips, n, ids ? ids[i] : i, clv_bytes_of(dtype, states, n));
-    if (rc == PLFX_OK && n == 0) rc = zero_sums(ctx, s, d.scaler_sum, 1);
-    if (rc != PLFX_OK) return rc;
-  }
-  if (n == 0 || count == 0) return PLFX_OK;
-  PLFX_WS(ctx, s, w);
-  if (states == 20 && tips == 2) {
-    // both children coded tips: the node's 576 code pairs through its own
-    // kernel, then x3 / scaler / sum gathered by code pair (a write stream;
-    // the direct kernel is compute-bound: 77 us f64, 95 us f32 per 2^18 sites)
-    if (!w->tt) {  // PLFX_CTX_LAZY_TABLES: this entry's tables on its first tip/tip use
-      if (w->capturing_now())
-        return fail(ctx, PLFX_ERR_INVALID,
-                    "protein tip/tip tables: the context was created with PLFX_CTX_LAZY_TABLES and "
-                    "this stream has not made a tip/tip call outside a capture yet");
-      void *t = nullptr;
-      hipError_t e = hipMallocAsync(&t, kTtEntryBytes, s);
-      if (e != hipSuccess)
-        return fail(ctx, PLFX_ERR_NOMEM, "tip/tip tables hipMallocAsync(%zu): %s", kTtEntryBytes,
-                    hipGetErrorString(e));
-      ctx->ws_blocks.push_back(t);
-      w->tt = static_cast<char *>(t);
-    }
-    char *tt = w->tt;
-    const uint8_t *cc1 = ctx->tt_codes, *cc2 = cc1 + 1024;
-    for (int j = 0; j < count; j += plfx::kMaxBatch) {
-      const int c = std::min(count - j, plfx::kMaxBatch);
-      plfx::NodeDescH comb[plfx::kMaxBatch];
-      plfx::ProtGatherDescH g[plfx::kMaxBatch];
-      for (int i = 0; i < c; i++) {
-        const plfx_node &d = nodes[j + i];
-        char *tab = tt + (size_t)i * (kTtTabBytes + kTtScBytes);
-        uint8_t *tsc = reinterpret_cast<uint8_t *>(tab + kTtTabBytes);
-        comb[i] = plfx::NodeDescH{cc1, cc2, tab, d.left, d.right, tsc, nullptr};
-        g[i] = plfx::ProtGatherDescH{static_cast<const uint8_t *>(d.x1), static_cast<const uint8_t *>(d.x2),
-                                     d.x3, d.scaler, d.scaler_sum, tab, tsc};
+// PLFX_CTX_LAZY_TABLES: the tip/tip tables of workspace entry w on its first
+// tip/tip use, before the call is lowered (its descriptors point into them)
+int ensure_tables(plfx_ctx *ctx, StreamWs *w, hipStream_t s) {
+  if (w->tt) return PLFX_OK;
+  if (w->capturing_now())
+    return fail(ctx, PLFX_ERR_INVALID,
+                "protein tip/tip tables: the context was created with PLFX_CTX_LAZY_TABLES and "
+                "this stream has not made a tip/tip call outside a capture yet");
+  void *t = nullptr;
+  hipError_t e = hipMallocAsync(&t, kTtEntryBytes, s);
+  if (e != hipSuccess)
+    return fail(ctx, PLFX_ERR_NOMEM, "tip/tip tables hipMallocAsync(%zu): %s", kTtEntryBytes,
+                hipGetErrorString(e));
+  ctx->ws_blocks.push_back(t);
+  w->tt = static_cast<char *>(t);
+  return PLFX_OK;
+}
+
+// The launches of a lowered call (trav_lower.hpp), in list order.
+int execute(plfx_ctx *ctx, const plfx::LaunchList &l, const ExecCall &c, unsigned long long *ws) {
+  const bool fma = (c.flags & PLFX_FMA) != 0;
+  const int mb = ctx->max_blocks;
+  for (const plfx::LaunchItem &it : l.items) {
+    hipError_t e = hipSuccess;
+    const char *what = "";
+    switch (it.kind) {
+      case plfx::kLaunchDeep:
+        what = "fused deep-subtree launch";
+        e = plfx::launch_plf_dna_deep(c.dtype, it.depth, &l.deeps[it.first], c.EV, c.wgt, c.n, ws, mb, c.s,
+                                      it.tips, c.tipvec);
+        break;
+      case plfx::kLaunchSeptets:
+        what = "fused three-level launch";
+        e = plfx::launch_plf_dna_septets(c.dtype, &l.septets[it.first], it.count, c.EV, c.wgt, c.n, ws, mb, c.s,
+                                         it.tips, c.tipvec);
+        break;
+      case plfx::kLaunchTriples:
+        what = "fused level-pair launch";
+        e = plfx::launch_plf_dna_triples(c.dtype, &l.triples[it.first], it.count, c.EV, c.wgt, c.n, ws, mb, c.s,
+                                         it.tips, c.tipvec);
+        break;
+      case plfx::kLaunchDnaBatch:
+        what = "plf batch launch";
+        e = plfx::launch_plf_dna_batch(c.dtype, &l.nodes[it.first], it.count, c.EV, c.wgt, c.n, ws, mb, c.s,
+                                       it.tips, c.tipvec, c.streams);
+        break;
+      case plfx::kLaunchProtNode: {
+        what = "plf_prot launch";
+        const plfx::NodeDescH &d = l.nodes[it.first];
+        plfx::DnaArgs a{d.x1, d.x2, d.x3, c.EV, d.left, d.right, c.wgt, d.scaler, d.scaler_sum, ws, c.n};
+        e = plfx::launch_plf_prot(c.dtype, fma, a, mb, c.s, it.tips, c.tipvec);
+        break;
       }
-      hipError_t e = plfx::launch_plf_prot_batch(dtype, fma, comb, c, EV, nullptr, plfx::kProtCombos, w->ws,
-                                                 ctx->max_blocks, s, 2, tipvec);
-      if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot combination tables");
-      e = plfx::launch_prot_tiptip_gather(dtype, g, c, wgt, n, w->ws, ctx->max_blocks, s);
-      if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot tip/tip gather");
-      if (launches) *launches += 2;
-      if (tabs) {  // this group's tables stay until the next group overwrites them
-        tabs->clear();
-        for (int i = 0; i < c; i++)
-          tabs->push_back(TabRef{nodes[j + i].x3, comb[i].x3, static_cast<const uint8_t *>(nodes[j + i].x1),
-                                 static_cast<const uint8_t *>(nodes[j + i].x2)});
-      }
+      case plfx::kLaunchProtBatch:
+        what = "plf_prot batch launch";
+        e = plfx::launch_plf_prot_batch(c.dtype, fma, &l.nodes[it.first], it.count, c.EV, c.wgt, c.n, ws, mb, c.s,
+                                        it.tips, c.tipvec);
+        break;
+      case plfx::kLaunchProtTipTip:
+        what = "plf_prot combination tables";
+        e = plfx::launch_plf_prot_batch(c.dtype, fma, &l.combs[it.first], it.count, c.EV, nullptr,
+                                        plfx::kProtCombos, ws, mb, c.s, 2, c.tipvec);
+        if (e != hipSuccess) break;
+        what = "plf_prot tip/tip gather";
+        e = plfx::launch_prot_tiptip_gather(c.dtype, &l.gathers[it.first], it.count, c.wgt, c.n, ws, mb, c.s);
+        break;
+      case plfx::kLaunchProtTab:
+        what = "plf_prot table-children launch";
+        e = plfx::launch_prot_tab_batch(c.dtype, fma, &l.tabs[it.first], it.count, c.EV, c.wgt, c.n, ws, mb, c.s);
+        break;
     }
-    return PLFX_OK;
-  }
-  if (states == 20 && count > 1) {
-    // protein: up to kMaxBatch nodes per launch, node = blockIdx.y, each node
-    // with the full resident grid so the nodes' blocks follow each other
-    // through the co-resident slots (the next node's blocks fill the CUs the
-    // previous node's last trips leave idle).  64-taxon tree at 2^18 sites per
-    // sweep vs one launch per node: f64 FMA 5.67 -> 5.38 ms, f64 exact 8.45 ->
-    // 8.02 ms, f32 FMA 2.94 -> 2.66 ms; splitting the resident grid over the
-    // nodes (the DNA batches' rule) gains only 1-3 % (tools/prot_batch_ab.py@f9b3af3,
-    // profiles/r03_protein_batch_ab.log).
-    const plfx::NodeDescH *all = reinterpret_cast<const plfx::NodeDescH *>(nodes);
-    for (int j = 0; j < count; j += plfx::kMaxBatch) {
-      const int c = std::min(count - j, plfx::kMaxBatch);
-      hipError_t e = plfx::launch_plf_prot_batch(dtype, fma, all + j, c, EV, wgt, n, w->ws, ctx->max_blocks,
-                                                 s, tips, tipvec);
-      if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot batch launch");
-      if (launches) ++*launches;
-    }
-    return PLFX_OK;
-  }
-  if (states == 20) {  // protein, one node: one full-GPU launch (plf_prot.hpp)
-    const plfx_node &d = nodes[0];
-    plfx::DnaArgs a{d.x1, d.x2, d.x3, EV, d.left, d.right, wgt, d.scaler, d.scaler_sum, w->ws, n};
-    hipError_t e = plfx::launch_plf_prot(dtype, fma, a, ctx->max_blocks, s, tips, tipvec);
-    if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot launch");
-    if (launches) ++*launches;
-    return PLFX_OK;
-  }
-  // More than kMaxBatch nodes: launch j takes nodes j, j + L, j + 2L, ... (L
-  // launches), so every launch mixes nodes from across the caller's list.
-  // Consecutive nodes are usually consecutive allocations, and a launch made of
-  // 32 neighbouring allocations of 128 MiB ran up to 15 % slower than a mixed
-  // one while each of its nodes alone ran at the same speed (nodes512 at N = 1:
-  // launches of 2.09-2.48 ms consecutive, 2.10-2.12 ms interleaved;
-  // tools/probes/nodes_groups.py, nodes_sched.py, HISTORY.md section 5).
-  const int L = (count + plfx::kMaxBatch - 1) / plfx::kMaxBatch;
-  const plfx::NodeDescH *all = reinterpret_cast<const plfx::NodeDescH *>(nodes);
-  for (int j = 0; j < L; j++) {
-    plfx::NodeDescH sel[plfx::kMaxBatch];
-    int c = 0;
-    for (int i = j; i < count; i += L) sel[c++] = all[i];
-    hipError_t e = plfx::launch_plf_dna_batch(dtype, L == 1 ? all : sel, c, EV, wgt, n, w->ws,
-                                              ctx->max_blocks, s, tips, tipvec, call.streams);
-    if (e != hipSuccess) return hip_fail(ctx, e, "plf batch launch");
-    if (launches) ++*launches;
+    if (e != hipSuccess) return hip_fail(ctx, e, what);
   }
   return PLFX_OK;
+}
+
+// Nodes of one kind (tips = number of tip children, tip child first):
+// lowered (trav_lower.hpp lower_batch), then launched.
+int run_batch(plfx_ctx *ctx, const ExecCall &c, const plfx_node *nodes, int count, int tips) {
+  if (count < 0 || c.n < 0 || (count > 0 && (!nodes || !c.EV)))
+    return fail(ctx, PLFX_ERR_INVALID, "bad batch arguments");
+  if (c.n == 0) {
+    for (int i = 0; i < count; i++)
+      if (int rc = zero_sums(ctx, c.s, nodes[i].scaler_sum, 1); rc != PLFX_OK) return rc;
+    return PLFX_OK;
+  }
+  if (count == 0) return PLFX_OK;
+  PLFX_WS(ctx, c.s, w);
+  if (c.states == 20 && tips == 2)
+    if (int rc = ensure_tables(ctx, w, c.s); rc != PLFX_OK) return rc;
+  std::string err;
+  const plfx::LowerCall lc{c.dtype, c.states, c.n, w->tt, ctx->tt_codes};
+  if (plfx::lower_batch(lc, nodes, count, tips, nullptr, &ctx->lowered, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  return execute(ctx, ctx->lowered, c, w->ws);
 }
 
 // The environment's settings of a new context; false for a value that is refused.
@@ -931,8 +824,8 @@ int plfx_plf_batch_dev(plfx_ctx *ctx, int dtype, int states, const plfx_node *no
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "batched nodes: states=%d not built (4, 20)", states);
   // DNA batches share the resident grid with the batches of the other
   // streams in flight (plfx_ctx_set_streams)
-  const BatchCall call{dtype, states, PLFX_EXACT, EV, n, wgt, /*tipvec*/ nullptr, pick(stream), ctx->streams};
-  return batch_impl(ctx, call, nodes, count, 0);
+  const ExecCall call{dtype, states, PLFX_EXACT, EV, n, wgt, /*tipvec*/ nullptr, pick(stream), ctx->streams};
+  return run_batch(ctx, call, nodes, count, 0);
 }
 
 int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const uint8_t *tip1,
@@ -954,8 +847,8 @@ int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const
     std::swap(nd.x1, nd.x2);
     std::swap(nd.left, nd.right);
   }
-  const BatchCall call{dtype, states, flags, EV, n, wgt, tipvec, pick(stream), /*streams*/ 1};
-  return batch_impl(ctx, call, &nd, 1, tips);
+  const ExecCall call{dtype, states, flags, EV, n, wgt, tipvec, pick(stream), /*streams*/ 1};
+  return run_batch(ctx, call, &nd, 1, tips);
 }
 
 int plfx_plf_tips_dev(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1,
@@ -1001,138 +894,25 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   int sched[PLFX_SCHED_COUNTS] = {};  // as plfx_traverse_schedule reports it; [6]: launches
   std::copy(plan.counts, plan.counts + 6, sched);
   hipStream_t s = pick(stream);
-  if (n == 0) {  // nothing to launch
+  if (n == 0 || nops == 0) {  // nothing to launch
     const int rc = zero_sums(ctx, s, scaler_sums, nops);
     if (rc != PLFX_OK) return rc;
     std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
     return PLFX_OK;
   }
-  unsigned long long *ws = nullptr;
-  if (nops > 0) {
-    PLFX_WS(ctx, s, w);
-    ws = w->ws;
-  }
-  const size_t cb = clv_bytes_of(dtype, states, n);
-  const TravNodes tn{ops, clv, tips, static_cast<const char *>(pmats),
-                     (size_t)states * states * 4 * (dtype == PLFX_F32 ? 4 : 8), scalers, scaler_sums};
+  // lower: every node checked, every descriptor filled, before the first launch
+  PLFX_WS(ctx, s, w);
+  const plfx::TravArrays arrays{ops, nops, clv, tips, pmats, scalers, scaler_sums};
+  if (plfx::traversal_uses_tables(arrays, states))
+    if (int rc = ensure_tables(ctx, w, s); rc != PLFX_OK) return rc;
+  const plfx::LowerCall lc{dtype, states, n, w->tt, ctx->tt_codes};
+  if (plfx::lower_traversal(plan, arrays, lc, &ctx->lowered, &plan_err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", plan_err.c_str());
   // execute: level by level, the level's fused groups first
-  std::vector<plfx_node> batch[3];  // by number of tip children
-  std::vector<int> bop[3];           // the op index of each batch entry
-  std::vector<plfx::TripleDescH> tb[3];
-  std::vector<plfx::SeptetDescH> sb[3];
-  // protein: the previous level's tip/tip nodes still in their
-  // combination tables; a node of this level whose two children are among them
-  // stages its child tiles from the tables (plf_prot.hpp kTab) instead of
-  // reading the children's CLVs back from HBM.  Only for the next level: later
-  // levels may overwrite the tables or the children's slots.
-  std::vector<TabRef> prev_tabs, cur_tabs;
-  const bool tab_mode = states == 20;
-  const BatchCall call{dtype, states, flags, EV, n, wgt, tipvec, s, /*streams*/ 1};
-  for (int lv = 0; lv < plan.nlev; lv++) {
-    for (int k = 0; k < 3; k++) {
-      batch[k].clear();
-      bop[k].clear();
-      tb[k].clear();
-      sb[k].clear();
-    }
-    // plan.groups holds the deep passes, then the septets, then the triples
-    for (const plfx::TravGroup &g : plan.groups) {
-      if (g.level != lv) continue;
-      if (g.kind == plfx::kTravSeptet) {
-        plfx::SeptetDescH d{};
-        const int rc = fill_fused(ctx, tn, g.ops.data(), 7, 4, n, cb, &d);
-        if (rc != PLFX_OK) return rc;
-        sb[g.tips].push_back(d);
-      } else if (g.kind == plfx::kTravTriple) {
-        const int a = g.ops[0], b = g.ops[1], p = g.ops[2];
-        int ka, kb, kp;
-        const plfx_node A = tn.node(a, &ka), B = tn.node(b, &kb), P = tn.node(p, &kp);
-        for (int rc : {check_node(ctx, A, ka, n, a, cb), check_node(ctx, B, kb, n, b, cb),
-                       check_node(ctx, P, kp, n, p, cb)})
-          if (rc != PLFX_OK) return rc;
-        // P's children as op P names them: child1 = A's slot or B's slot
-        const bool a_first = ops[p].child1 == ops[a].parent;
-        const plfx_node &F = a_first ? A : B, &G = a_first ? B : A;
-        tb[g.tips].push_back(plfx::TripleDescH{
-            F.x1, F.x2, G.x1, G.x2, F.x3, G.x3, P.x3, (const double *)F.left,
-            (const double *)F.right, (const double *)G.left, (const double *)G.right,
-            (const double *)P.left, (const double *)P.right, F.scaler, G.scaler, P.scaler,
-            F.scaler_sum, G.scaler_sum, P.scaler_sum});
-      } else {  // a deep pass: one launch each, ahead of the level's other work
-        const int D = 6 - g.kind;
-        plfx::DeepDescH d{};
-        const int rc = fill_fused(ctx, tn, g.ops.data(), (1 << D) - 1, 1 << (D - 1), n, cb, &d);
-        if (rc != PLFX_OK) return rc;
-        hipError_t e = plfx::launch_plf_dna_deep(dtype, D, &d, EV, wgt, n, ws, ctx->max_blocks, s,
-                                                 g.tips, tipvec);
-        if (e != hipSuccess) return hip_fail(ctx, e, "fused deep-subtree launch");
-        sched[6]++;
-      }
-    }
-    for (int j = 0; j < nops; j++) {
-      if (plan.level[j] != lv || plan.fused[j]) continue;
-      int kind;
-      const plfx_node nd = tn.node(j, &kind);
-      batch[kind].push_back(nd);
-      bop[kind].push_back(j);
-    }
-    for (int k = 0; k < 3; k++) {
-      for (size_t i = 0; i < sb[k].size(); i += plfx::kMaxSeptets) {
-        const int c = (int)std::min<size_t>(plfx::kMaxSeptets, sb[k].size() - i);
-        hipError_t e = plfx::launch_plf_dna_septets(dtype, sb[k].data() + i, c, EV, wgt, n,
-                                                    ws, ctx->max_blocks, s, k, tipvec);
-        if (e != hipSuccess) return hip_fail(ctx, e, "fused three-level launch");
-        sched[6]++;
-      }
-      for (size_t i = 0; i < tb[k].size(); i += plfx::kMaxTriples) {
-        const int c = (int)std::min<size_t>(plfx::kMaxTriples, tb[k].size() - i);
-        hipError_t e = plfx::launch_plf_dna_triples(dtype, tb[k].data() + i, c, EV, wgt, n, ws,
-                                                    ctx->max_blocks, s, k, tipvec);
-        if (e != hipSuccess) return hip_fail(ctx, e, "fused level-pair launch");
-        sched[6]++;
-      }
-      if (k == 0 && tab_mode && !prev_tabs.empty() && !batch[0].empty()) {
-        auto find = [&](const void *x) -> const TabRef * {
-          for (const TabRef &t : prev_tabs)
-            if (t.x3 == x) return &t;
-          return nullptr;
-        };
-        std::vector<plfx::ProtTabDescH> tab;
-        std::vector<plfx_node> rest;
-        std::vector<int> rest_op;
-        for (size_t q = 0; q < batch[0].size(); q++) {
-          const plfx_node &nd = batch[0][q];
-          const TabRef *a = find(nd.x1), *b = find(nd.x2);
-          if (!a || !b) {
-            rest.push_back(nd);
-            rest_op.push_back(bop[0][q]);
-            continue;
-          }
-          // these nodes do not go through batch_impl's checks: checked here
-          const int rc = check_node(ctx, nd, 0, n, bop[0][q], cb);
-          if (rc != PLFX_OK) return rc;
-          tab.push_back(plfx::ProtTabDescH{a->tab, b->tab, a->ca, a->cb, b->ca, b->cb, nd.x3, nd.left,
-                                           nd.right, nd.scaler, nd.scaler_sum});
-        }
-        for (size_t i = 0; i < tab.size(); i += plfx::kMaxBatch) {
-          const int c = (int)std::min<size_t>(plfx::kMaxBatch, tab.size() - i);
-          hipError_t e = plfx::launch_prot_tab_batch(dtype, (flags & PLFX_FMA) != 0, tab.data() + i, c, EV,
-                                                     wgt, n, ws, ctx->max_blocks, s);
-          if (e != hipSuccess) return hip_fail(ctx, e, "plf_prot table-children launch");
-          sched[6]++;
-        }
-        batch[0].swap(rest);
-        bop[0].swap(rest_op);
-      }
-      if (batch[k].empty()) continue;
-      int rc = batch_impl(ctx, call, batch[k].data(), (int)batch[k].size(), k, bop[k].data(), &sched[6],
-                          k == 2 && tab_mode ? &cur_tabs : nullptr);
-      if (rc != PLFX_OK) return rc;
-    }
-    prev_tabs.swap(cur_tabs);
-    cur_tabs.clear();
-  }
-  for (int i = 0; i < PLFX_SCHED_COUNTS; i++) ctx->sched[i] = sched[i];
+  const ExecCall call{dtype, states, flags, EV, n, wgt, tipvec, s, /*streams*/ 1};
+  if (int rc = execute(ctx, ctx->lowered, call, w->ws); rc != PLFX_OK) return rc;
+  sched[6] = ctx->lowered.launches();
+  std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
   return PLFX_OK;
 }
 

@@ -7,7 +7,9 @@ Three things: the schedules of the trees the GPU suite runs are pinned
 Context.last_schedule() reports for them); every plan over random trees and
 forests with recycled slots replays hazard-free -- each op reads exactly the
 slot versions it reads in sequential order when all items of a level run
-concurrently; and the groups have the shape the kernels' descriptors assume."""
+concurrently; and the groups have the shape the kernels' descriptors assume.
+The same replay over the launches in the order the library issues them is
+tests/test_trav_lower.py's."""
 import os
 import subprocess
 from pathlib import Path
@@ -53,16 +55,19 @@ def planner(tmp_path_factory):
             if w[0] == "error":
                 cur = {"error": (int(w[1]), ln.split(" ", 2)[2])}
             elif w[0] == "counts":
-                cur = {"counts": [int(x) for x in w[1:]], "levels": []}
-            elif w[0] == "level":
-                assert int(w[1]) == len(cur["levels"])
-                cur["levels"].append([])
+                cur = {"counts": [int(x) for x in w[1:]]}
+            elif w[0] == "levels":
+                cur["levels"] = [[] for _ in range(int(w[1]))]
+                cur["level"], fused = [int(x) for x in w[2:]], set()
             elif w[0] == "group":
-                cur["levels"][-1].append((w[1], int(w[2]), [int(x) for x in w[3:]]))
-            elif w[0] == "op":
-                cur["levels"][-1].append(("op", None, [int(w[1])]))
+                cur["levels"][int(w[3])].append((w[1], int(w[2]), [int(x) for x in w[4:]]))
+                fused |= {int(x) for x in w[4:]}
             else:
                 assert w == ["end"], ln
+                if "error" not in cur:  # a level's items: its groups, then its unfused ops
+                    for j, lv in enumerate(cur["level"]):
+                        if j not in fused:
+                            cur["levels"][lv].append(("op", None, [j]))
                 out.append(cur)
         assert len(out) == len(cases)
         return out

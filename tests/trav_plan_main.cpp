@@ -7,11 +7,12 @@
 //   nops lines "parent child1 child2 pmat"
 // stdout per case:
 //   counts deep6 deep5 deep4 septets triples unfused
-//   level L                      then the level's items in issue order:
-//   group KIND TIPS op op ...    (KIND deep6|deep5|deep4|septet|triple)
-//   op J                         (an unfused op)
+//   levels NLEV l l ...               (the level of every op)
+//   group KIND TIPS LEVEL op op ...   (KIND deep6|deep5|deep4|septet|triple)
 //   end
 // or, for a refused op list: "error CODE text", then "end".
+// The order the launches are issued in is csrc/trav_lower.cpp's
+// (tests/trav_lower_main.cpp).
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -43,25 +44,13 @@ int main() {
     printf("counts");
     for (int c : plan.counts) printf(" %d", c);
     printf("\n");
-    // the issue order of plfx_traverse_tips within a level: the deep passes,
-    // then by number of tip children k: septets, triples, unfused ops
-    for (int lv = 0; lv < plan.nlev; lv++) {
-      printf("level %d\n", lv);
-      auto group = [&](const plfx::TravGroup &g) {
-        printf("group %s %d", kKind[g.kind], g.tips);
-        for (int j : g.ops) printf(" %d", j);
-        printf("\n");
-      };
-      for (const plfx::TravGroup &g : plan.groups)
-        if (g.level == lv && g.kind <= plfx::kTravDeep4) group(g);
-      for (int k = 0; k < 3; k++) {
-        for (int kind : {plfx::kTravSeptet, plfx::kTravTriple})
-          for (const plfx::TravGroup &g : plan.groups)
-            if (g.level == lv && g.kind == kind && g.tips == k) group(g);
-        for (int j = 0; j < nops; j++)
-          if (plan.level[j] == lv && !plan.fused[j] && tip[ops[j].child1] + tip[ops[j].child2] == k)
-            printf("op %d\n", j);
-      }
+    printf("levels %d", plan.nlev);
+    for (int lv : plan.level) printf(" %d", lv);
+    printf("\n");
+    for (const plfx::TravGroup &g : plan.groups) {
+      printf("group %s %d %d", kKind[g.kind], g.tips, g.level);
+      for (int j : g.ops) printf(" %d", j);
+      printf("\n");
     }
     printf("end\n");
   }
