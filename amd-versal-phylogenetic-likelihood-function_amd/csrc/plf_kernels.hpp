@@ -104,6 +104,28 @@ hipError_t launch_edge_optimize(int dtype, int states, const void *const *sumtab
                                 void *state, double *partials, unsigned long long *ws, double *t_opt,
                                 double *out3, int32_t *evals, int max_blocks, hipStream_t s);
 
+// Per-site rate categories (plf_psr.hpp; defined in plf_psr.hip =
+// libplfx_psr.so, which libplfx.so links): DNA, one of ncat (1..32) categories
+// per site from the device bytes rate_cat, CLVs of n * 4 values.  Node: count
+// <= kMaxBatch nodes of one kind per launch, tips bit 0 / 1 = child 1 / 2 of
+// every node is coded (its descriptor pointer names uint8 codes), left / right
+// of ncat * 16 values, ws as launch_plf_dna_batch's.  Root lnL, sum table and
+// edge sums: as their Gamma counterparts above, partials / ticket included.
+hipError_t launch_plf_psr(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
+                          const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n, const void *tipvec,
+                          unsigned long long *ws, int max_blocks, hipStream_t s);
+hipError_t launch_root_lnl_psr(int dtype, const void *x, int64_t n, const double *freq, const int32_t *wgt,
+                               const int64_t *scaler_sums, int nsums, double *partials,
+                               unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,
+                               hipStream_t s);
+hipError_t launch_edge_sumtable_psr(int dtype, bool tip, const void *x1, const void *x2, int64_t n,
+                                    const void *tipvec, void *sumtab, int max_blocks, hipStream_t s);
+hipError_t launch_edge_derivatives_psr(int dtype, const void *sumtab, int64_t n, const double *lambda,
+                                       const double *rates, int ncat, const uint8_t *rate_cat,
+                                       const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                                       double *partials, unsigned long long *ticket, double *out3,
+                                       double *site_lnl, int max_blocks, hipStream_t s);
+
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,
                              hipStream_t s);

@@ -1,0 +1,117 @@
+// plf_psr.hip -- launchers of the per-site-rate kernels (plf_psr.hpp: the DNA
+// node, the root lnL, the sum table and the edge sums with one rate category
+// per site, plfx.h section 11).
+//
+// Built into a library of its own, plfx/libplfx_psr.so, which libplfx.so
+// links, as plf_edge.hip is: libplfx.so's code objects and the pinned kernel
+// list (tests/golden/kernel_symbols.txt) stay as they are.  The C ABI
+// (plfx_*_psr*) is in plfx_api.hip like every other entry point.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#define PLFX_SECONDARY_TU  // plf_dna.hpp's non-template kernel lives in plf_kernels.hip
+#include "plf_psr.hpp"
+#include "plf_kernels.hpp"
+#include "plf_launch.hpp"
+
+namespace plfx {
+namespace {
+
+using dev::kBlock;
+static_assert(kBlockThreads == kBlock, "block size mismatch");
+static_assert(dev::kMaxBatch == kMaxBatch && dev::kWsWords == kWsWords, "batch constants");
+using bools = among<false, true>;
+
+// sites per lane and trip: 128 B (f64) / 64 B (f32) of child loads in flight per lane
+template <typename T>
+constexpr int kNodeU = sizeof(T) == 8 ? 2 : 4;
+constexpr int kStreamU = 4;  // root lnL, edge sums: one 32-B / 16-B load per site
+
+// The node is an HBM stream: the share of the co-resident blocks its node
+// count leaves each node (grid_x), node = blockIdx.y.
+template <typename T, bool T1, bool T2>
+hipError_t launch_plf_psr_t(const NodeDescH *nodes, int count, const void *EV, const uint8_t *rate_cat, int ncat,
+                            const int32_t *wgt, int64_t n, const void *tipvec, unsigned long long *ws,
+                            int max_blocks, hipStream_t s) {
+  constexpr int U = kNodeU<T>;
+  const auto p = pack<dev::NodeBatch>(nodes, count, [](const NodeDescH &d) { return d.scaler_sum != nullptr; });
+  static int cache[2] = {0, 0};
+  auto go = [&](auto kSum) {
+    auto kernel = &dev::plf_psr_kernel<T, U, kSum(), T1, T2>;
+    const int64_t gx = grid_x((const void *)kernel, cache[kSum() ? 1 : 0], n, kBlock * U, count, max_blocks);
+    return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, p.b, (const T *)EV, rate_cat, ncat, wgt,
+                  n, ws, (const T *)tipvec);
+  };
+  return p.any_sum ? go(std::true_type{}) : go(std::false_type{});
+}
+
+template <typename K>
+int64_t lnl_grid(K kernel, int &cache, int64_t n, int max_blocks) {
+  return std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock * kStreamU, 1, max_blocks), kLnlMaxGrid);
+}
+
+}  // namespace
+
+hipError_t launch_plf_psr(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
+                          const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n, const void *tipvec,
+                          unsigned long long *ws, int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch || ncat < 1 || ncat > dev::kPsrMaxCats || n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64, auto kT1, auto kT2) {
+        return launch_plf_psr_t<real_t<k64()>, kT1(), kT2()>(nodes, count, EV, rate_cat, ncat, wgt, n, tipvec, ws,
+                                                            max_blocks, s);
+      },
+      bools{dtype == 1}, bools{(tips & 1) != 0}, bools{(tips & 2) != 0});
+}
+
+hipError_t launch_root_lnl_psr(int dtype, const void *x, int64_t n, const double *freq, const int32_t *wgt,
+                               const int64_t *scaler_sums, int nsums, double *partials,
+                               unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,
+                               hipStream_t s) {
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::root_lnl_psr_kernel<T, kStreamU>;
+        const int64_t gx = lnl_grid(kernel, cache, n, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, freq, wgt, scaler_sums, nsums,
+                      partials, ticket, out, site_lnl);
+      },
+      bools{dtype == 1});
+}
+
+hipError_t launch_edge_sumtable_psr(int dtype, bool tip, const void *x1, const void *x2, int64_t n,
+                                    const void *tipvec, void *sumtab, int max_blocks, hipStream_t s) {
+  return dispatch(
+      [&](auto k64, auto kTip) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::edge_sumtable_psr_kernel<T, kTip()>;
+        constexpr int kSitesPerTrip = kBlock * 4 / (4 * (int)sizeof(T) / 16);
+        const int64_t gx = grid_x((const void *)kernel, cache, n, kSitesPerTrip, 1, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, x1, (const T *)x2, n, (const T *)tipvec, (T *)sumtab);
+      },
+      bools{dtype == 1}, bools{tip});
+}
+
+hipError_t launch_edge_derivatives_psr(int dtype, const void *sumtab, int64_t n, const double *lambda,
+                                       const double *rates, int ncat, const uint8_t *rate_cat,
+                                       const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                                       double *partials, unsigned long long *ticket, double *out3,
+                                       double *site_lnl, int max_blocks, hipStream_t s) {
+  if (ncat < 1 || ncat > dev::kPsrMaxCats) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::edge_deriv_psr_kernel<T, kStreamU>;
+        const int64_t gx = lnl_grid(kernel, cache, n, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)sumtab, n, lambda, rates, ncat, rate_cat,
+                      wgt, t, scaler_sums, nsums, partials, ticket, out3, site_lnl);
+      },
+      bools{dtype == 1});
+}
+
+}  // namespace plfx

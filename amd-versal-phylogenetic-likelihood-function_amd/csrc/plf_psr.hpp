@@ -1,0 +1,333 @@
+// plf_psr.hpp -- device code of the per-site-rate (PSR, "CAT") DNA mode,
+// plfx.h section 11: every site belongs to exactly one of ncat rate
+// categories, so a CLV is x[site*4 + state] -- a quarter of the Gamma layout
+// -- and a site's P matrices are chosen by its category byte,
+// c = min(rate_cat[site], ncat - 1).
+//
+// Node update, in plf()'s operation order with no contraction:
+//   umpL[k] = sum_l x1[i][l] * left[c*16 + k*4 + l]   (from +0.0, ascending l)
+//   x3[i][l] = sum_k (umpL[k] * umpR[k]) * EV[4k + l] (from +0.0, ascending k)
+// then the 2^-32 rescale over the site's four values.  One lane owns one site:
+// its children are 16 (f32) or 32 (f64) contiguous bytes, the scale test needs
+// no cross-lane step, and the only thing that is not wave-uniform any more --
+// the two matrices -- comes from LDS, where the block stages both tables once.
+//
+// LDS rows.  A lane reads its category's 16 values per side as ds_read_b128
+// (16-lane groups, sixteen 16-B slots per LDS cycle).  With the natural row
+// stride (128 B in f64, 64 B in f32) chunk j of every row falls on 2 (f64) or
+// 4 (f32) of the sixteen slots, so a group whose lanes sit in different
+// categories would serialise 8- or 4-fold.  One 16-B chunk of padding per row
+// makes the stride 9 (f64) or 5 (f32) slots, odd, so 16 consecutive
+// categories cover all sixteen slots: what is left is the chance collision of
+// random categories (ncat / 16 rows share a slot).  EV is wave-uniform and
+// stays in scalar registers.
+//
+// A coded child's ump depends only on (category, code): the block forms
+// tab[(c*16 + code)*4 + k] = sum_l tipvec[code][l] * P_c[k][l] in the same
+// order, so results are bit-identical to the dense computation on the
+// expanded child (as plf_dna.hpp build_tip_table does per Gamma category).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <type_traits>
+
+#include "plf_edge.hpp"
+
+namespace plfx {
+namespace dev {
+
+constexpr int kPsrMaxCats = 32;  // PLFX_PSR_MAX_CATS (asserted in plfx_api.hip)
+
+template <typename T>
+struct PsrRow {
+  static constexpr int kChunk = 16 / (int)sizeof(T);  // values per 16-B chunk
+  static constexpr int kStride = 16 + kChunk;         // values per staged matrix row (one chunk of padding)
+  using V = std::conditional_t<sizeof(T) == 8, f64x2, f32x4>;
+};
+
+__device__ __forceinline__ int psr_cat(int byte, int ncat) { return byte < ncat ? byte : ncat - 1; }
+
+// both tables of a node into LDS, padded rows; the caller synchronises
+template <typename T>
+__device__ __forceinline__ void psr_stage(const T *__restrict__ P, int ncat, T *sP) {
+  for (int i = threadIdx.x; i < ncat * 16; i += kBlock) sP[(i >> 4) * PsrRow<T>::kStride + (i & 15)] = P[i];
+}
+
+// tab[(c*16 + code)*4 + k] of a coded child (tv NULL: the 0/1 indicator)
+template <typename T>
+__device__ __forceinline__ void psr_tip_table(const T *__restrict__ P, const T *__restrict__ tv, int ncat,
+                                              T *tab) {
+  for (int i = threadIdx.x; i < ncat * 64; i += kBlock) {
+    const int c = i >> 6, code = (i >> 2) & 15, k = i & 3;
+    T v = T(0);
+#pragma unroll
+    for (int l = 0; l < 4; l++) v += (tv ? tv[code * 4 + l] : T((code >> l) & 1)) * P[c * 16 + k * 4 + l];
+    tab[i] = v;
+  }
+}
+
+// a 16-B aligned LDS row of N values as 16-B reads
+template <typename T, int N>
+__device__ __forceinline__ void psr_lds_row(const T *row, T (&m)[N]) {
+  using V = typename PsrRow<T>::V;
+  constexpr int kChunk = PsrRow<T>::kChunk;
+  static_assert(N % kChunk == 0, "whole chunks");
+  const V *r = reinterpret_cast<const V *>(row);
+#pragma unroll
+  for (int j = 0; j < N / kChunk; j++) {
+    const V v = r[j];
+#pragma unroll
+    for (int e = 0; e < kChunk; e++) m[j * kChunk + e] = v[e];
+  }
+}
+
+// Up to kMaxBatch nodes per launch, node = blockIdx.y, sharing EV, n, wgt and
+// rate_cat; T1 / T2: child 1 / 2 of every node of the launch is coded (the
+// descriptor's x1 / x2 then point at uint8 codes).  U sites per lane and trip,
+// all their loads issued first (clamped to the last site, results unused past
+// n).  kSum: some node of the launch wants its weighted scaler sum.
+template <typename T, int U, bool kSum, bool T1, bool T2>
+__global__ void __launch_bounds__(kBlock)
+plf_psr_kernel(const NodeBatch nodes, const T *__restrict__ EV, const uint8_t *__restrict__ rate_cat, int ncat,
+               const int32_t *__restrict__ wgt, int64_t n, unsigned long long *ws,
+               const T *__restrict__ tipvec) {
+  constexpr int kStride = PsrRow<T>::kStride;
+  const NodeDesc &d = nodes.d[blockIdx.y];
+  const T *__restrict__ x1 = static_cast<const T *>(d.x1);
+  const T *__restrict__ x2 = static_cast<const T *>(d.x2);
+  const uint8_t *__restrict__ tip1 = static_cast<const uint8_t *>(d.x1);
+  const uint8_t *__restrict__ tip2 = static_cast<const uint8_t *>(d.x2);
+  T *__restrict__ x3 = static_cast<T *>(d.x3);
+  uint8_t *__restrict__ scaler = d.scaler;
+  unsigned long long *wsn = ws + (size_t)blockIdx.y * kWsWords;
+
+  __shared__ __attribute__((aligned(16))) T sL[T1 ? 4 : kPsrMaxCats * kStride];
+  __shared__ __attribute__((aligned(16))) T sR[T2 ? 4 : kPsrMaxCats * kStride];
+  __shared__ __attribute__((aligned(16))) T tab1[T1 ? kPsrMaxCats * 64 : 4];
+  __shared__ __attribute__((aligned(16))) T tab2[T2 ? kPsrMaxCats * 64 : 4];
+  if constexpr (T1) psr_tip_table<T>(static_cast<const T *>(d.left), tipvec, ncat, tab1);
+  else psr_stage<T>(static_cast<const T *>(d.left), ncat, sL);
+  if constexpr (T2) psr_tip_table<T>(static_cast<const T *>(d.right), tipvec, ncat, tab2);
+  else psr_stage<T>(static_cast<const T *>(d.right), ncat, sR);
+  __syncthreads();
+
+  T E[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) E[i] = EV[i];  // uniform: scalar loads
+  const T m = Num<T>::minlik();
+
+  long long acc = 0;
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < n; base += stride) {
+    T a[U][4], b[U][4];
+    int cat[U], k1[U], k2[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int64_t ld = site < n ? site : nlast;
+      cat[u] = rate_cat[ld];
+      if constexpr (T1) k1[u] = tip1[ld] & 15;
+      else Num<T>::template load4<true>(x1 + ld * 4, a[u]);
+      if constexpr (T2) k2[u] = tip2[ld] & 15;
+      else Num<T>::template load4<true>(x2 + ld * 4, b[u]);
+      if (kSum) w[u] = wgt_at(wgt, ld, ws);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int c = psr_cat(cat[u], ncat);
+      T u1[4], u2[4];
+      if constexpr (T1) {
+        psr_lds_row<T, 4>(tab1 + (c * 16 + k1[u]) * 4, u1);
+      } else {
+        T PL[16];
+        psr_lds_row<T, 16>(sL + c * kStride, PL);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          u1[k] = T(0);
+#pragma unroll
+          for (int l = 0; l < 4; l++) u1[k] += a[u][l] * PL[k * 4 + l];
+        }
+      }
+      if constexpr (T2) {
+        psr_lds_row<T, 4>(tab2 + (c * 16 + k2[u]) * 4, u2);
+      } else {
+        T PR[16];
+        psr_lds_row<T, 16>(sR + c * kStride, PR);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          u2[k] = T(0);
+#pragma unroll
+          for (int l = 0; l < 4; l++) u2[k] += b[u][l] * PR[k * 4 + l];
+        }
+      }
+      T o[4] = {T(0), T(0), T(0), T(0)};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const T p = u1[k] * u2[k];
+#pragma unroll
+        for (int l = 0; l < 4; l++) o[l] += p * E[4 * k + l];
+      }
+      const bool sc = (Num<T>::abs(o[0]) < m) && (Num<T>::abs(o[1]) < m) && (Num<T>::abs(o[2]) < m) &&
+                      (Num<T>::abs(o[3]) < m);
+#pragma unroll
+      for (int l = 0; l < 4; l++) {
+        const T s = o[l] * Num<T>::two32();  // exact: power-of-two scaling
+        o[l] = sc ? s : o[l];
+      }
+      if (site < n) {
+        Num<T>::store4_nt(x3 + site * 4, o);
+        if (scaler) scaler[site] = (uint8_t)sc;
+        if (kSum) acc += sc ? (long long)w[u] : 0ll;
+      }
+    }
+  }
+  if constexpr (kSum) block_ticket_sum(acc, wsn, d.scaler_sum);
+}
+
+// Root lnL of a PSR CLV: L_i = sum_s freq[s] * x[i][s] (from +0.0, ascending
+// s, in f64), one lane per site, U sites per lane and trip; the sum over the
+// sites through plf_lnl.hpp's fixed-order reduction.
+template <typename T, int U>
+__global__ void __launch_bounds__(kBlock)
+root_lnl_psr_kernel(const T *__restrict__ x, int64_t n, const double *__restrict__ freq,
+                    const int32_t *__restrict__ wgt, const int64_t *__restrict__ scaler_sums, int nsums,
+                    double *partials, unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+  double fr[4];
+#pragma unroll
+  for (int s = 0; s < 4; s++) fr[s] = freq ? freq[s] : 0.25;
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < n; base += stride) {
+    T v[U][4];
+    int w[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int64_t ld = site < n ? site : nlast;
+      Num<T>::template load4<true>(x + ld * 4, v[u]);
+      w[u] = wgt_at(wgt, ld, partials);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      double L = 0.0;
+#pragma unroll
+      for (int s = 0; s < 4; s++) L += fr[s] * (double)v[u][s];
+      if (site < n) {
+        const double l = log(L);
+        if (site_lnl) site_lnl[site] = l;
+        acc += (double)w[u] * l;
+      }
+    }
+  }
+  lnl_finish(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+// Sum table of a PSR branch: x1 * x2 over n * 4 values, 16-B chunks, U chunks
+// per thread and trip (plf_edge.hpp edge_sumtable_kernel for one category).
+// kTip: side 1 is one code per site, x1[i][k] = tipvec[(code & 15)*4 + k].
+template <typename T, bool kTip>
+__global__ void __launch_bounds__(kBlock)
+edge_sumtable_psr_kernel(const void *__restrict__ x1, const T *__restrict__ x2, int64_t n,
+                         const T *__restrict__ tipvec, T *__restrict__ out) {
+  using V = typename PsrRow<T>::V;
+  constexpr int kVals = PsrRow<T>::kChunk;
+  constexpr int kSite = 4 / kVals;  // chunks per site
+  constexpr int U = 4;
+  const int64_t total = n * kSite;
+  const V *a = static_cast<const V *>(x1);
+  const uint8_t *codes = static_cast<const uint8_t *>(x1);
+  const V *b = reinterpret_cast<const V *>(x2);
+  V *o = reinterpret_cast<V *>(out);
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < total; base += stride) {
+    V va[U], vb[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t j = base + u * kBlock + threadIdx.x;
+      if (j >= total) continue;
+      vb[u] = __builtin_nontemporal_load(b + j);
+      if constexpr (kTip) {
+        const int64_t site = j / kSite;
+        const T *tv = tipvec + (codes[site] & 15) * 4 + (int)(j - site * kSite) * kVals;
+#pragma unroll
+        for (int e = 0; e < kVals; e++) va[u][e] = tv[e];
+      } else {
+        va[u] = __builtin_nontemporal_load(a + j);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t j = base + u * kBlock + threadIdx.x;
+      if (j < total) __builtin_nontemporal_store(va[u] * vb[u], o + j);
+    }
+  }
+}
+
+// The three edge sums of a PSR branch.  x_k = lambda_k * rates[c_i]; the
+// ncat x 4 factor triples {e, e x, e x x} are formed once per block from the
+// device t into LDS (rows of 12 doubles padded to 14: a stride of 7 slots,
+// odd, as the node's tables) and a lane reads its site's row.  L, L1, L2 =
+// sum_k st[i][k] * {e, e1, e2} from +0.0, ascending k, in f64; the sums over
+// the sites as plf_edge.hpp's (edge_site, lnl_finish<3>).  n == 0: one block,
+// out = {correction, 0, 0}.
+constexpr int kPsrFactorStride = 14;
+template <typename T, int U>
+__global__ void __launch_bounds__(kBlock)
+edge_deriv_psr_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
+                      const double *__restrict__ rates, int ncat, const uint8_t *__restrict__ rate_cat,
+                      const int32_t *__restrict__ wgt, const double *__restrict__ tp,
+                      const int64_t *__restrict__ scaler_sums, int nsums, double *partials,
+                      unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+  __shared__ __attribute__((aligned(16))) double tab[kPsrMaxCats * kPsrFactorStride];
+  const double t = *tp;
+  for (int i = threadIdx.x; i < ncat * 4; i += kBlock) {
+    const int c = i >> 2, k = i & 3;
+    double e0, e1, e2;
+    edge_factors(lambda[k], rates[c], t, e0, e1, e2);
+    tab[c * kPsrFactorStride + k] = e0;
+    tab[c * kPsrFactorStride + 4 + k] = e1;
+    tab[c * kPsrFactorStride + 8 + k] = e2;
+  }
+  __syncthreads();
+  double acc[3] = {0.0, 0.0, 0.0};
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < n; base += stride) {
+    T v[U][4];
+    int cat[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int64_t ld = site < n ? site : nlast;
+      cat[u] = rate_cat[ld];
+      Num<T>::template load4<true>(st + ld * 4, v[u]);
+      w[u] = wgt_at(wgt, ld, partials);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      double f[12];
+      psr_lds_row<double, 12>(tab + psr_cat(cat[u], ncat) * kPsrFactorStride, f);
+      double L = 0.0, L1 = 0.0, L2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const double x = (double)v[u][k];
+        L += x * f[k];
+        L1 += x * f[4 + k];
+        L2 += x * f[8 + k];
+      }
+      if (site < n) {
+        const double l = edge_site(L, L1, L2, w[u], acc);
+        if (site_lnl) site_lnl[site] = l;
+      }
+    }
+  }
+  lnl_finish<3>(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+}  // namespace dev
+}  // namespace plfx

@@ -19,6 +19,7 @@
 #include "../../include/plfx.h"
 #include "edge_newton.hpp"
 #include "plf_kernels.hpp"
+#include "psr_lower.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
 #include "trav_lower.hpp"
@@ -56,6 +57,7 @@ struct plfx_ctx {
   double *edge_buf = nullptr;       // plfx_edge_optimize: the trial t and the three results (kEdgeBufBytes)
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
   plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
+  plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -536,6 +538,48 @@ int check_edge_args(plfx_ctx *ctx, int dtype, int states, const void *sumtab, in
   if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
   if (!eigen || !rates || (n > 0 && !sumtab)) return fail(ctx, PLFX_ERR_INVALID, "edge: null sum table / eigen / rates");
   if (!aligned16(sumtab)) return fail(ctx, PLFX_ERR_INVALID, "the sum table must be 16-byte aligned");
+  return PLFX_OK;
+}
+
+// the arguments plfx_edge_derivatives_psr and plfx_edge_optimize_psr share
+int check_psr_edge_args(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                        const double *rates, int ncat, const uint8_t *rate_cat) {
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (ncat < 1 || ncat > PLFX_PSR_MAX_CATS)
+    return fail(ctx, PLFX_ERR_INVALID, "psr edge: ncat=%d outside 1..%d", ncat, PLFX_PSR_MAX_CATS);
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  if (!eigen || !rates || (n > 0 && (!sumtab || !rate_cat)))
+    return fail(ctx, PLFX_ERR_INVALID, "psr edge: null sum table / eigen / rates / rate_cat");
+  if (!aligned16(sumtab)) return fail(ctx, PLFX_ERR_INVALID, "the sum table must be 16-byte aligned");
+  return PLFX_OK;
+}
+
+// The host-synchronous bracketed Newton of plfx_edge_optimize and
+// plfx_edge_optimize_psr (edge_newton.hpp) from t0 on stream s: eval(d_t,
+// d_out) enqueues one evaluation of the three sums at the device double d_t
+// into the device doubles d_out, both in the context's edge_buf.
+template <typename Eval>
+int edge_newton_loop(plfx_ctx *ctx, const char *who, double t0, double tmin, double tmax, int max_evals,
+                     double *t_opt, double *out3_host, int *evals, hipStream_t s, Eval eval) {
+  if (!t_opt) return fail(ctx, PLFX_ERR_INVALID, "%s: null t_opt", who);
+  plfx::EdgeNewton step(t0, tmin, tmax, max_evals);
+  if (!step.valid())
+    return fail(ctx, PLFX_ERR_INVALID, "%s: needs 0 < tmin <= t0 <= tmax and max_evals >= 1", who);
+  if (capturing(s))
+    return fail(ctx, PLFX_ERR_INVALID, "%s waits for every evaluation: not on a capturing stream", who);
+  double *d_t = ctx->edge_buf, *d_out = ctx->edge_buf + 1;
+  double t = 0.0, out[3] = {0.0, 0.0, 0.0};
+  for (bool more = true; more;) {
+    t = step.t();  // read by the upload until the wait below
+    PLFX_HIP(ctx, hipMemcpyAsync(d_t, &t, sizeof t, hipMemcpyHostToDevice, s));
+    if (int rc = eval(d_t, d_out); rc != PLFX_OK) return rc;
+    PLFX_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, s));
+    PLFX_HIP(ctx, hipStreamSynchronize(s));
+    more = step.advance(out[1], out[2]);
+  }
+  *t_opt = t;
+  if (out3_host) std::copy(out, out + 3, out3_host);
+  if (evals) *evals = step.evals();
   return PLFX_OK;
 }
 
@@ -1022,29 +1066,11 @@ int plfx_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab,
                        double *t_opt, double *out3_host, int *evals, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_edge_args(ctx, dtype, states, sumtab, n, eigen, rates, ncat); rc != PLFX_OK) return rc;
-  if (!t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize: null t_opt");
-  plfx::EdgeNewton step(t0, tmin, tmax, max_evals);
-  if (!step.valid())
-    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize: needs 0 < tmin <= t0 <= tmax and max_evals >= 1");
-  hipStream_t s = pick(stream);
-  if (capturing(s))
-    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize waits for every evaluation: not on a capturing stream");
-  double *d_t = ctx->edge_buf, *d_out = ctx->edge_buf + 1;
-  double t = 0.0, out[3] = {0.0, 0.0, 0.0};
-  for (bool more = true; more;) {
-    t = step.t();  // read by the upload until the wait below
-    PLFX_HIP(ctx, hipMemcpyAsync(d_t, &t, sizeof t, hipMemcpyHostToDevice, s));
-    int rc = plfx_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, catw, wgt, d_t, nullptr, 0,
-                                   d_out, nullptr, stream);
-    if (rc != PLFX_OK) return rc;
-    PLFX_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, s));
-    PLFX_HIP(ctx, hipStreamSynchronize(s));
-    more = step.advance(out[1], out[2]);
-  }
-  *t_opt = t;
-  if (out3_host) std::copy(out, out + 3, out3_host);
-  if (evals) *evals = step.evals();
-  return PLFX_OK;
+  return edge_newton_loop(ctx, "edge_optimize", t0, tmin, tmax, max_evals, t_opt, out3_host, evals, pick(stream),
+                          [&](const double *d_t, double *d_out) {
+                            return plfx_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, catw, wgt,
+                                                         d_t, nullptr, 0, d_out, nullptr, stream);
+                          });
 }
 
 int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
@@ -1075,6 +1101,105 @@ int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *con
     if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_dev launch");
   }
   return PLFX_OK;
+}
+
+// ---- (11) per-site rate categories ----
+
+int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
+                     int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
+                     void *stream) {
+  PLFX_BIND(ctx);
+  static_assert(PLFX_PSR_MAX_CATS <= 256, "a category is one byte");
+  std::string err;
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat};
+  if (plfx::lower_psr(call, nodes, count, &ctx->psr_lowered, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  hipStream_t s = pick(stream);
+  if (n == 0) {
+    for (int i = 0; i < count; i++)
+      if (int rc = zero_sums(ctx, s, nodes[i].scaler_sum, 1); rc != PLFX_OK) return rc;
+    return PLFX_OK;
+  }
+  PLFX_WS(ctx, s, w);
+  for (const plfx::PsrLaunch &it : ctx->psr_lowered.items) {
+    hipError_t e = plfx::launch_plf_psr(dtype, it.tips, &ctx->psr_lowered.nodes[it.first], it.count, EV, rate_cat,
+                                        ncat, wgt, n, tipvec, w->ws, ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "plf_psr launch");
+  }
+  return PLFX_OK;
+}
+
+int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                      double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (!out_lnl || n < 0 || (n > 0 && !x) || nsums < 0 || (nsums > 0 && !scaler_sums))
+    return fail(ctx, PLFX_ERR_INVALID, "bad root_lnl_psr arguments");
+  if (!aligned16(x)) return fail(ctx, PLFX_ERR_INVALID, "the CLV must be 16-byte aligned");
+  hipStream_t s = pick(stream);
+  if (n == 0) {
+    const int rc = zero_sums(ctx, s, out_lnl, 1);
+    if (rc != PLFX_OK || nsums == 0) return rc;
+  }
+  PLFX_WS(ctx, s, w);
+  hipError_t e = plfx::launch_root_lnl_psr(dtype, x, n, freq, wgt, scaler_sums, nsums, w->lnl_partials,
+                                           w->lnl_ticket, out_lnl, site_lnl, ctx->max_blocks, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "root_lnl_psr launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
+                           int64_t n, const void *tipvec, void *sumtab, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if ((tip1 != nullptr) == (x1 != nullptr))
+    return fail(ctx, PLFX_ERR_INVALID, "side 1 needs exactly one of tip / CLV");
+  if (tip1 && !tipvec)
+    return fail(ctx, PLFX_ERR_INVALID, "a coded side needs tipvec (the default 0/1 table is not in eigen coordinates)");
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  if (n == 0) return PLFX_OK;
+  if (!x2 || !sumtab) return fail(ctx, PLFX_ERR_INVALID, "null CLV / sum table pointer");
+  if ((x1 && !aligned16(x1)) || !aligned16(x2) || !aligned16(sumtab))
+    return fail(ctx, PLFX_ERR_INVALID, "CLV pointers must be 16-byte aligned");
+  const size_t cb = plfx::psr_clv_bytes(dtype, n);
+  if (overlap(sumtab, cb, tip1 ? (const void *)tip1 : x1, tip1 ? (size_t)n : cb) || overlap(sumtab, cb, x2, cb))
+    return fail(ctx, PLFX_ERR_INVALID, "sumtab may not overlap x1/x2");
+  hipError_t e = plfx::launch_edge_sumtable_psr(dtype, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2, n,
+                                                tipvec, sumtab, ctx->max_blocks, pick(stream));
+  if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
+                              double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
+  if (!t || !out3 || nsums < 0 || (nsums > 0 && !scaler_sums))
+    return fail(ctx, PLFX_ERR_INVALID, "bad edge_derivatives_psr arguments");
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // n == 0 launches too: one block, out3 = {correction, 0, 0}
+  hipError_t e = plfx::launch_edge_derivatives_psr(dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t,
+                                                   scaler_sums, nsums, w->lnl_partials, w->lnl_ticket, out3,
+                                                   site_lnl, ctx->max_blocks, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "edge_derivatives_psr launch");
+  return PLFX_OK;
+}
+
+int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
+                           double *out3_host, int *evals, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
+  return edge_newton_loop(ctx, "edge_optimize_psr", t0, tmin, tmax, max_evals, t_opt, out3_host, evals, pick(stream),
+                          [&](const double *d_t, double *d_out) {
+                            return plfx_edge_derivatives_psr(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt,
+                                                             d_t, nullptr, 0, d_out, nullptr, stream);
+                          });
 }
 
 }  // extern "C"

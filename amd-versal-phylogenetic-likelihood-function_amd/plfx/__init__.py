@@ -54,8 +54,11 @@ EXPORTS = (
     "plfx_pmatrix", "plfx_model_tip_vectors",
     "plfx_shard", "plfx_gen_hostmem", "plfx_swemu_instance_run", "plfx_traverse_schedule",
     "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize", "plfx_edge_optimize_dev",
+    "plfx_plf_psr_dev", "plfx_root_lnl_psr", "plfx_edge_sumtable_psr", "plfx_edge_derivatives_psr",
+    "plfx_edge_optimize_psr",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
+PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
 MAX_STREAMS = 64   # PLFX_MAX_STREAMS
 WS_POOL = 8        # PLFX_WS_POOL
 STREAMS_MAX = 8    # PLFX_STREAMS_MAX
@@ -78,6 +81,13 @@ class Node(C.Structure):
     """plfx_node: one inner-node update (all device pointers)."""
     _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p), ("x3", C.c_void_p),
                 ("left", C.c_void_p), ("right", C.c_void_p), ("scaler", C.c_void_p),
+                ("scaler_sum", C.c_void_p)]
+
+
+class PsrNode(C.Structure):
+    """plfx_psr_node: one per-site-rate node (all device pointers)."""
+    _fields_ = [("tip1", C.c_void_p), ("x1", C.c_void_p), ("tip2", C.c_void_p), ("x2", C.c_void_p),
+                ("x3", C.c_void_p), ("left", C.c_void_p), ("right", C.c_void_p), ("scaler", C.c_void_p),
                 ("scaler_sum", C.c_void_p)]
 
 
@@ -169,6 +179,12 @@ def load():
                                      dp, dp, C.POINTER(i32), vp]
     L.plfx_edge_optimize_dev.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl,
                                          i32, vp, vp, vp, vp]
+    L.plfx_plf_psr_dev.argtypes = [vp, i32, C.POINTER(PsrNode), i32, vp, i64, vp, i32, vp, vp, vp]
+    L.plfx_root_lnl_psr.argtypes = [vp, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
+    L.plfx_edge_sumtable_psr.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, vp]
+    L.plfx_edge_derivatives_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.plfx_edge_optimize_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32, dp, dp,
+                                         C.POINTER(i32), vp]
     _lib = L
     return L
 
@@ -739,6 +755,158 @@ class Context:
         tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
         self._check(self._L.plfx_edge_optimize_dev(*args[:3], tabs, m, *args[4:], p(t0), float(tmin), float(tmax),
                                                    int(max_evals), p(t_opt), p(out3), p(evals), self._sh(stream)))
+
+    # -- (11) per-site rate categories ---------------------------------------
+    @staticmethod
+    def _psr_states(states):
+        if states != 4:
+            raise PlfxError(ERR_UNSUPPORTED, f"per-site rate categories: states={states} not built (4)")
+
+    @staticmethod
+    def _psr_cats(rate_cat, n):
+        import torch
+
+        if (rate_cat is None or rate_cat.dtype != torch.uint8 or rate_cat.numel() < n or not rate_cat.is_cuda
+                or not rate_cat.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "rate_cat must be a contiguous uint8 device tensor of >= n elements")
+
+    def plf_psr(self, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, states=4, stream=None):
+        """Per-site-rate node updates (plfx.h section 11).  nodes: one dict or
+        a list of dicts with x3, left, right and, per child, exactly one of
+        x1 / tip1 and one of x2 / tip2 (dense CLVs of 4*n values, or uint8
+        codes), plus optional scaler, scaler_sum.  rate_cat: uint8 device
+        tensor, one category per site (values >= ncat count as ncat - 1);
+        left / right hold ncat * 16 values."""
+        import torch
+
+        self._psr_states(states)
+        if isinstance(nodes, dict):
+            nodes = [nodes]
+        n, ncat = int(n), int(ncat)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        if not EV.is_cuda or EV.numel() < 16:
+            raise PlfxError(ERR_INVALID, "EV must be a device tensor of 16 values")
+        self._psr_cats(rate_cat, n)
+        _check_aux(n, wgt, None, None)
+        arr = (PsrNode * max(1, len(nodes)))()
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        for i, nd in enumerate(nodes):
+            for k in ("x1", "x2", "x3"):
+                t = nd.get(k)
+                if t is not None and (t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda):
+                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= 4*n")
+            for k in ("tip1", "tip2"):
+                t = nd.get(k)
+                if t is not None and (t.dtype != torch.uint8 or t.numel() < n or not t.is_contiguous()
+                                      or not t.is_cuda):
+                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous uint8 device tensor >= n")
+            for k in ("left", "right"):
+                t = nd.get(k)
+                if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()
+                                      or t.numel() < 16 * max(ncat, 0)):
+                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor of ncat*16 values")
+            _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
+            arr[i] = PsrNode(*(p(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
+                                                       "scaler", "scaler_sum")))
+        self._check(self._L.plfx_plf_psr_dev(
+            self.h, F32 if dt == torch.float32 else F64, arr, len(nodes), C.c_void_p(EV.data_ptr()), n,
+            C.c_void_p(rate_cat.data_ptr()), ncat, C.c_void_p(p(wgt)), self._tipvec(tipvec, dt), self._sh(stream)))
+
+    def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
+                     stream=None):
+        """Root lnL of a per-site-rate CLV into `out` (float64 device tensor,
+        1 element); plfx.h section 11."""
+        import torch
+
+        self._psr_states(states)
+        if out.dtype != torch.float64 or out.numel() < 1 or not out.is_cuda:
+            raise PlfxError(ERR_INVALID, "out must be a float64 device tensor")
+        if (x.dtype not in (torch.float32, torch.float64) or x.numel() < 4 * n or not x.is_cuda
+                or not x.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "x must be a contiguous float device tensor of >= 4*n values")
+        for t, k in ((freq, 4), (site_lnl, n)):
+            if t is not None and (t.dtype != torch.float64 or t.numel() < k or not t.is_cuda
+                                  or not t.is_contiguous()):
+                raise PlfxError(ERR_INVALID, "freq/site_lnl must be contiguous float64 device tensors (4 / n values)")
+        _check_aux(n, wgt, None, None)
+        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
+                                        or not scaler_sums.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        nsums = 0 if scaler_sums is None else scaler_sums.numel()
+        self._check(self._L.plfx_root_lnl_psr(self.h, F32 if x.dtype == torch.float32 else F64, p(x), int(n),
+                                              p(freq), p(wgt), p(scaler_sums), nsums, p(out), p(site_lnl),
+                                              self._sh(stream)))
+
+    def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
+        """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the
+        dense CLV x1 or the uint8 codes tip1 with the eigen-convention table."""
+        import torch
+
+        self._psr_states(states)
+        dt = sumtab.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
+            if t is not None and (t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= 4*n")
+        if tip1 is not None and (tip1.dtype != torch.uint8 or tip1.numel() < n or not tip1.is_contiguous()
+                                 or not tip1.is_cuda):
+            raise PlfxError(ERR_INVALID, "tip1 must be a contiguous uint8 device tensor >= n")
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        self._check(self._L.plfx_edge_sumtable_psr(self.h, F32 if dt == torch.float32 else F64, p(tip1), p(x1),
+                                                   p(x2), int(n), self._tipvec(tipvec, dt), p(sumtab),
+                                                   self._sh(stream)))
+
+    def _edge_args_psr(self, sumtab, n, eigen, rates, rate_cat, wgt, states):
+        import torch
+
+        self._psr_states(states)
+        if (sumtab.dtype not in (torch.float32, torch.float64) or sumtab.numel() < 4 * n
+                or not sumtab.is_cuda or not sumtab.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "sumtab must be a contiguous float device tensor of >= 4*n values")
+        for k, t, m in (("eigen", eigen, 4), ("rates", rates, 1)):
+            if t.dtype != torch.float64 or t.numel() < m or not t.is_cuda or not t.is_contiguous():
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor")
+        self._psr_cats(rate_cat, n)
+        _check_aux(n, wgt, None, None)
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        return (self.h, F32 if sumtab.dtype == torch.float32 else F64, p(sumtab), int(n), p(eigen), p(rates),
+                rates.numel(), p(rate_cat), p(wgt))
+
+    def edge_derivatives_psr(self, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None, scaler_sums=None,
+                             site_lnl=None, states=4, stream=None):
+        """out (float64 device tensor, 3 elements) = lnL, d lnL/dt, d2 lnL/dt2 of
+        the per-site-rate branch whose sum table is `sumtab`, at the device
+        double `t`; rates holds the ncat category rates (plfx.h section 11)."""
+        import torch
+
+        args = self._edge_args_psr(sumtab, n, eigen, rates, rate_cat, wgt, states)
+        for k, x, m in (("t", t, 1), ("out", out, 3), ("site_lnl", site_lnl, n)):
+            if x is not None and (x.dtype != torch.float64 or x.numel() < m or not x.is_cuda
+                                  or not x.is_contiguous()):
+                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor of >= {m}")
+        if t is None or out is None:
+            raise PlfxError(ERR_INVALID, "t and out are required")
+        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
+                                        or not scaler_sums.is_contiguous()):
+            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
+        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
+        nsums = 0 if scaler_sums is None else scaler_sums.numel()
+        self._check(self._L.plfx_edge_derivatives_psr(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl),
+                                                      self._sh(stream)))
+
+    def optimize_branch_psr(self, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0, max_evals=64,
+                            wgt=None, states=4, stream=None):
+        """optimize_branch for a per-site-rate branch (plfx_edge_optimize_psr,
+        host-synchronous).  Returns (t, lnL, d1, d2, evals)."""
+        args = self._edge_args_psr(sumtab, n, eigen, rates, rate_cat, wgt, states)
+        t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
+        self._check(self._L.plfx_edge_optimize_psr(*args, float(t0), float(tmin), float(tmax), int(max_evals),
+                                                   C.byref(t), out, C.byref(ev), self._sh(stream)))
+        return t.value, out[0], out[1], out[2], ev.value
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):

@@ -583,6 +583,94 @@ int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *con
                            double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
                            void *stream);
 
+/* ---- (11) per-site rate categories (PSR) -- the GTRCAT model of RAxML /
+ * ExaML next to the Gamma model of every section above (extension) ----------
+ * Every site belongs to exactly ONE of ncat rate categories, so a PSR CLV is
+ * x[site*4 + state] -- n * 4 values, a quarter of the Gamma layout, 16-byte
+ * aligned -- and a node's P matrices are chosen per site.  DNA (4 states)
+ * only, f32 and f64; there is no states argument (the Python binding answers
+ * a protein request with PLFX_ERR_UNSUPPORTED).
+ *   rate_cat: device uint8[n]; site i uses category min(rate_cat[i], ncat-1)
+ *             (the clamp of protein tip codes >= 24: no index leaves a table);
+ *   ncat:     1 <= ncat <= PLFX_PSR_MAX_CATS, else PLFX_ERR_INVALID;
+ *   left, right: ncat * 16 values of dtype, [c][k][l] -- what plfx_pmatrix
+ *             writes per branch for `ncat` rates.
+ * Node update, with c the site's category, in plf()'s operation order and
+ * with no FMA contraction:
+ *   umpL[k]  = sum_l x1[i][l] * left[c*16 + k*4 + l]     (same for right / x2)
+ *   x3[i][l] = sum_k (umpL[k] * umpR[k]) * EV[4k + l]
+ * then, if all FOUR |x3[i][.]| < 2^-32 (strict; NaN never scales), they are
+ * multiplied by 2^32, scaler[i] = 1 and wgt[i] is added to the node's scaler
+ * sum: plf()'s loop with one category, run on each category's sites with that
+ * category's matrices, bit for bit.  A child is dense or coded as in section
+ * (8): uint8 codes, x[i][s] = tipvec[(code & 15)*4 + s], tipvec a device table
+ * of 16 x 4 values of dtype or NULL (the 0/1 indicator); results are
+ * bit-identical to the dense computation on the expanded child. */
+#define PLFX_PSR_MAX_CATS 32
+
+/* One PSR node: exactly one of tip1 / x1 and one of tip2 / x2 is non-NULL;
+ * scaler (uint8 per site) and scaler_sum (int64) are optional.  All device
+ * pointers. */
+typedef struct {
+  const uint8_t *tip1;
+  const void *x1;
+  const uint8_t *tip2;
+  const void *x2;
+  void *x3;
+  const void *left, *right;
+  uint8_t *scaler;
+  int64_t *scaler_sum;
+} plfx_psr_node;
+
+/* count >= 1 independent nodes sharing EV, n, rate_cat, wgt and tipvec.  The
+ * `nodes` array is host memory and travels in the kernel arguments (nodes of
+ * one kind of children, up to 32 per launch, node = blockIdx.y, as
+ * plfx_plf_batch_dev): asynchronous, allocates nothing, capture-safe as
+ * plfx_plf_batch_dev; count == 1 is the one-node call.  Every check runs
+ * before the first launch: PLFX_ERR_INVALID for count < 1, n < 0, ncat out of
+ * range, a null EV / rate_cat / nodes, and per node for both or neither of
+ * tip / dense on a side, a null x3 / left / right, a dense child or x3 not
+ * 16-byte aligned, and an x3 that shares a byte with a child it reads.  n ==
+ * 0: nothing is launched and the nodes' scaler sums are zeroed. */
+int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
+                     int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
+                     void *stream);
+
+/* lnL = sum_i wgt_i * log( sum_s freq[s] * x[i][s] )
+ *       + (sum_{j<nsums} scaler_sums[j]) * log(2^-32)
+ * x: the root's PSR CLV; the other arguments, the fixed-order reduction and
+ * the capture rules are plfx_root_lnl's (freq NULL = 1/4 each; there are no
+ * category weights: a site has one category). */
+int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                      double *site_lnl, void *stream);
+
+/* Section (10) for a PSR branch; the CLVs must be in the eigen convention as
+ * there.  Sum table: sumtab[i][k] = x1[i][k] * x2[i][k], one multiply rounded
+ * in dtype, n * 4 values; side 1 dense or coded (tipvec required with tip1),
+ * alignment and overlap rules of plfx_edge_sumtable. */
+int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
+                           int64_t n, const void *tipvec, void *sumtab, void *stream);
+
+/* out3 as plfx_edge_derivatives', in f64, with x_k = lambda_k * rates[c_i], e
+ * = exp(x_k t), and L, L1, L2 = sum_k sumtab[i][k] * {e, e x, e x x}
+ * (ascending k).  rates: device, ncat doubles; rate_cat, ncat as above
+ * (PLFX_ERR_INVALID outside 1..PLFX_PSR_MAX_CATS); the factors are formed
+ * from the device t once per thread block.  n == 0: out3 = {correction, 0, 0}.
+ * Deterministic, asynchronous, capture-safe as plfx_edge_derivatives. */
+int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
+                              double *site_lnl, void *stream);
+
+/* plfx_edge_optimize over plfx_edge_derivatives_psr: the same bracketed Newton
+ * iteration, stop rules, argument rules and refusal of a capturing stream;
+ * host-synchronous.  (There is no device-resident PSR loop.) */
+int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
+                           double *out3_host, int *evals, void *stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
