@@ -114,6 +114,13 @@ hipError_t launch_edge_optimize(int dtype, int states, const void *const *sumtab
 hipError_t launch_plf_psr(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
                           const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n, const void *tipvec,
                           unsigned long long *ws, int max_blocks, hipStream_t s);
+// Fused PSR level pairs (plf_psr.hpp plf_psr_triple_kernel): count <=
+// kMaxTriples per launch, ws >= 3 * count regions; tips 0 / 1 / 2 = the
+// number of coded children of each leaf op, coded child first; every matrix
+// of ncat * 16 values.
+hipError_t launch_plf_psr_triples(int dtype, int tips, const TripleDescH *t, int count, const void *EV,
+                                  const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n,
+                                  const void *tipvec, unsigned long long *ws, int max_blocks, hipStream_t s);
 hipError_t launch_root_lnl_psr(int dtype, const void *x, int64_t n, const double *freq, const int32_t *wgt,
                                const int64_t *scaler_sums, int nsums, double *partials,
                                unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,

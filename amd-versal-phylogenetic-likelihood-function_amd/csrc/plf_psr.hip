@@ -47,6 +47,25 @@ hipError_t launch_plf_psr_t(const NodeDescH *nodes, int count, const void *EV, c
   return p.any_sum ? go(std::true_type{}) : go(std::false_type{});
 }
 
+// Fused level pairs: a triple's share of the co-resident blocks, triple =
+// blockIdx.y, the node kernel's sites per lane and trip.
+template <typename T, int kTips>
+hipError_t launch_plf_psr_triples_t(const TripleDescH *t, int count, const void *EV, const uint8_t *rate_cat,
+                                    int ncat, const int32_t *wgt, int64_t n, const void *tipvec,
+                                    unsigned long long *ws, int max_blocks, hipStream_t s) {
+  constexpr int U = kNodeU<T>;
+  static_assert(dev::PsrTripleLds<T, kTips>::kValues * sizeof(T) <= 160 * 1024, "LDS of a gfx950 workgroup");
+  const auto p = pack<dev::TripleBatch>(t, count, [](const TripleDescH &d) { return d.ssa || d.ssb || d.ssp; });
+  static int cache[2] = {0, 0};
+  auto go = [&](auto kSum) {
+    auto kernel = &dev::plf_psr_triple_kernel<T, U, kSum(), kTips>;
+    const int64_t gx = grid_x((const void *)kernel, cache[kSum() ? 1 : 0], n, kBlock * U, count, max_blocks);
+    return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, p.b, (const T *)EV, rate_cat, ncat, wgt,
+                  n, ws, (const T *)tipvec);
+  };
+  return p.any_sum ? go(std::true_type{}) : go(std::false_type{});
+}
+
 template <typename K>
 int64_t lnl_grid(K kernel, int &cache, int64_t n, int max_blocks) {
   return std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock * kStreamU, 1, max_blocks), kLnlMaxGrid);
@@ -64,6 +83,19 @@ hipError_t launch_plf_psr(int dtype, int tips, const NodeDescH *nodes, int count
                                                             max_blocks, s);
       },
       bools{dtype == 1}, bools{(tips & 1) != 0}, bools{(tips & 2) != 0});
+}
+
+hipError_t launch_plf_psr_triples(int dtype, int tips, const TripleDescH *t, int count, const void *EV,
+                                  const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n,
+                                  const void *tipvec, unsigned long long *ws, int max_blocks, hipStream_t s) {
+  static_assert(dev::kMaxTriples == kMaxTriples, "triple batch size");
+  if (count < 1 || count > kMaxTriples || ncat < 1 || ncat > dev::kPsrMaxCats || n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64, auto kTips) {
+        return launch_plf_psr_triples_t<real_t<k64()>, kTips()>(t, count, EV, rate_cat, ncat, wgt, n, tipvec, ws,
+                                                                max_blocks, s);
+      },
+      bools{dtype == 1}, among<0, 1, 2>{tips});
 }
 
 hipError_t launch_root_lnl_psr(int dtype, const void *x, int64_t n, const double *freq, const int32_t *wgt,

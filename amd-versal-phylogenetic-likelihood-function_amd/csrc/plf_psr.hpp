@@ -186,6 +186,177 @@ plf_psr_kernel(const NodeBatch nodes, const T *__restrict__ EV, const uint8_t *_
   if constexpr (kSum) block_ticket_sum(acc, wsn, d.scaler_sum);
 }
 
+// One site of one node, plf_psr_kernel's arithmetic restated for the fused
+// kernel below (the node kernel keeps its own statement: routed through this
+// function its register allocation changes, f64 dense/dense 91 -> 112 VGPRs):
+// o = the (possibly rescaled) parent values, returns the site's scale flag.  row1 / row2: the side's LDS row -- the category's padded
+// matrix row (dense child a / b) or the 4 products of (category, code) when
+// the side is coded (T1 / T2; a / b are then unused).
+template <typename T, bool T1, bool T2>
+__device__ __forceinline__ bool psr_site(const T (&a)[4], const T (&b)[4], const T *row1, const T *row2,
+                                         const T (&E)[16], T m, T (&o)[4]) {
+  T u1[4], u2[4];
+  if constexpr (T1) {
+    psr_lds_row<T, 4>(row1, u1);
+  } else {
+    T PL[16];
+    psr_lds_row<T, 16>(row1, PL);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      u1[k] = T(0);
+#pragma unroll
+      for (int l = 0; l < 4; l++) u1[k] += a[l] * PL[k * 4 + l];
+    }
+  }
+  if constexpr (T2) {
+    psr_lds_row<T, 4>(row2, u2);
+  } else {
+    T PR[16];
+    psr_lds_row<T, 16>(row2, PR);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      u2[k] = T(0);
+#pragma unroll
+      for (int l = 0; l < 4; l++) u2[k] += b[l] * PR[k * 4 + l];
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < 4; l++) o[l] = T(0);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const T p = u1[k] * u2[k];
+#pragma unroll
+    for (int l = 0; l < 4; l++) o[l] += p * E[4 * k + l];
+  }
+  const bool sc = (Num<T>::abs(o[0]) < m) && (Num<T>::abs(o[1]) < m) && (Num<T>::abs(o[2]) < m) &&
+                  (Num<T>::abs(o[3]) < m);
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    const T s = o[l] * Num<T>::two32();  // exact: power-of-two scaling
+    o[l] = sc ? s : o[l];
+  }
+  return sc;
+}
+
+// Fused level pair of a PSR traversal (plfx_traverse_psr): ops A and B of one
+// level and the op P of the next that reads both, in one pass.  The lane that
+// owns a site computes A from (a1, a2) and B from (b1, b2) as psr_site does,
+// stores both, and computes P from the (rescaled) values it still holds, so
+// P's children are written once and never read back: 4 leaf reads + 3 writes
+// per site instead of 6 reads + 3 writes.  Every node keeps its own scale
+// test, scaler byte and weighted sum: the bits of three plf_psr_kernel
+// launches.  Up to kMaxTriples per launch, triple = blockIdx.y, each with
+// three consecutive ticket regions of ws.
+// kTips: 0 the four leaves are dense; 1 a1 and b1 are coded (the lowering puts
+// the coded child first); 2 all four are coded.  LDS: a (category, code) table
+// per coded leaf, a padded matrix table per dense leaf, and P's two matrix
+// tables -- in f64 at most 27 KB (kTips 0), 50 KB (1), 73 KB (2), half of
+// that in f32.
+template <typename T, int kTips>
+struct PsrTripleLds {
+  static constexpr int kMat = kPsrMaxCats * PsrRow<T>::kStride;  // a staged matrix table
+  static constexpr int kTab = kPsrMaxCats * 64;                  // a coded leaf's table
+  static constexpr int kSide1 = kTips >= 1 ? kTab : kMat, kSide2 = kTips == 2 ? kTab : kMat;
+  static constexpr int kValues = 2 * kSide1 + 2 * kSide2 + 2 * kMat;
+};
+
+template <typename T, int U, bool kSum, int kTips>
+__global__ void __launch_bounds__(kBlock)
+plf_psr_triple_kernel(const TripleBatch tb, const T *__restrict__ EV, const uint8_t *__restrict__ rate_cat,
+                      int ncat, const int32_t *__restrict__ wgt, int64_t n, unsigned long long *ws,
+                      const T *__restrict__ tipvec) {
+  constexpr bool T1 = kTips >= 1, T2 = kTips == 2;
+  constexpr int kStride = PsrRow<T>::kStride;
+  using Lds = PsrTripleLds<T, kTips>;
+  const TripleDesc &d = tb.d[blockIdx.y];
+
+  __shared__ __attribute__((aligned(16))) T lds[Lds::kValues];
+  T *const sA1 = lds, *const sB1 = sA1 + Lds::kSide1, *const sA2 = sB1 + Lds::kSide1;
+  T *const sB2 = sA2 + Lds::kSide2, *const sLP = sB2 + Lds::kSide2, *const sRP = sLP + Lds::kMat;
+  if constexpr (T1) {
+    psr_tip_table<T>((const T *)d.la, tipvec, ncat, sA1);
+    psr_tip_table<T>((const T *)d.lb, tipvec, ncat, sB1);
+  } else {
+    psr_stage<T>((const T *)d.la, ncat, sA1);
+    psr_stage<T>((const T *)d.lb, ncat, sB1);
+  }
+  if constexpr (T2) {
+    psr_tip_table<T>((const T *)d.ra, tipvec, ncat, sA2);
+    psr_tip_table<T>((const T *)d.rb, tipvec, ncat, sB2);
+  } else {
+    psr_stage<T>((const T *)d.ra, ncat, sA2);
+    psr_stage<T>((const T *)d.rb, ncat, sB2);
+  }
+  psr_stage<T>((const T *)d.lp, ncat, sLP);
+  psr_stage<T>((const T *)d.rp, ncat, sRP);
+  __syncthreads();
+
+  T E[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) E[i] = EV[i];  // uniform: scalar loads
+  const T m = Num<T>::minlik();
+  const T *__restrict__ xa1 = (const T *)d.a1, *__restrict__ xa2 = (const T *)d.a2;
+  const T *__restrict__ xb1 = (const T *)d.b1, *__restrict__ xb2 = (const T *)d.b2;
+  const uint8_t *__restrict__ ta1 = (const uint8_t *)d.a1, *__restrict__ ta2 = (const uint8_t *)d.a2;
+  const uint8_t *__restrict__ tb1 = (const uint8_t *)d.b1, *__restrict__ tb2 = (const uint8_t *)d.b2;
+  T *__restrict__ xa = (T *)d.xa, *__restrict__ xb = (T *)d.xb, *__restrict__ xp = (T *)d.xp;
+
+  long long accA = 0, accB = 0, accP = 0;
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < n; base += stride) {
+    T va1[U][4], va2[U][4], vb1[U][4], vb2[U][4];
+    int cat[U], ka1[U], ka2[U], kb1[U], kb2[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int64_t ld = site < n ? site : nlast;
+      cat[u] = rate_cat[ld];
+      if constexpr (T1) {
+        ka1[u] = ta1[ld] & 15;
+        kb1[u] = tb1[ld] & 15;
+      } else {
+        Num<T>::template load4<true>(xa1 + ld * 4, va1[u]);
+        Num<T>::template load4<true>(xb1 + ld * 4, vb1[u]);
+      }
+      if constexpr (T2) {
+        ka2[u] = ta2[ld] & 15;
+        kb2[u] = tb2[ld] & 15;
+      } else {
+        Num<T>::template load4<true>(xa2 + ld * 4, va2[u]);
+        Num<T>::template load4<true>(xb2 + ld * 4, vb2[u]);
+      }
+      if (kSum) w[u] = wgt_at(wgt, ld, ws);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int c = psr_cat(cat[u], ncat);
+      T oA[4], oB[4], oP[4];
+      const bool sA = psr_site<T, T1, T2>(va1[u], va2[u], T1 ? sA1 + (c * 16 + ka1[u]) * 4 : sA1 + c * kStride,
+                                          T2 ? sA2 + (c * 16 + ka2[u]) * 4 : sA2 + c * kStride, E, m, oA);
+      const bool sB = psr_site<T, T1, T2>(vb1[u], vb2[u], T1 ? sB1 + (c * 16 + kb1[u]) * 4 : sB1 + c * kStride,
+                                          T2 ? sB2 + (c * 16 + kb2[u]) * 4 : sB2 + c * kStride, E, m, oB);
+      const bool sP = psr_site<T, false, false>(oA, oB, sLP + c * kStride, sRP + c * kStride, E, m, oP);
+      if (site < n) {
+        Num<T>::store4_nt(xa + site * 4, oA);
+        Num<T>::store4_nt(xb + site * 4, oB);
+        Num<T>::store4_nt(xp + site * 4, oP);
+        if (d.sa) d.sa[site] = (uint8_t)sA;
+        if (d.sb) d.sb[site] = (uint8_t)sB;
+        if (d.sp) d.sp[site] = (uint8_t)sP;
+        if (kSum) {
+          accA += sA ? (long long)w[u] : 0ll;
+          accB += sB ? (long long)w[u] : 0ll;
+          accP += sP ? (long long)w[u] : 0ll;
+        }
+      }
+    }
+  }
+  if constexpr (kSum)
+    block_ticket_sum3(accA, accB, accP, ws + (size_t)blockIdx.y * 3 * kWsWords, d.ssa, d.ssb, d.ssp);
+}
+
 // Root lnL of a PSR CLV: L_i = sum_s freq[s] * x[i][s] (from +0.0, ascending
 // s, in f64), one lane per site, U sites per lane and trip; the sum over the
 // sites through plf_lnl.hpp's fixed-order reduction.

@@ -20,6 +20,7 @@
 #include "edge_newton.hpp"
 #include "plf_kernels.hpp"
 #include "psr_lower.hpp"
+#include "psr_trav_lower.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
 #include "trav_lower.hpp"
@@ -50,6 +51,8 @@ struct plfx_ctx {
   int streams = 1;                  // one-node calls kept in flight (plfx_ctx_set_streams, PLFX_STREAMS)
   int fuse = 3;  // traverse: 3 six-level subtrees before 2's, 2 three-level subtrees +
                  // level pairs, 1 level pairs, 0 none (PLFX_FUSE)
+  int psr_fuse = 0;  // traverse_psr: >= 1 level pairs, 0 none.  PLFX_FUSE when it is set; unset means 0 here
+                     // (level pairs lose at 2^14 sites), not `fuse`'s default
   bool lazy_tables = false;         // PLFX_CTX_LAZY_TABLES
   plfx::WsPool wss{hipStreamPerThread};  // per-stream workspaces
   std::vector<void *> ws_blocks;    // their allocations (the pool's, then one per extra entry)
@@ -58,6 +61,7 @@ struct plfx_ctx {
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
   plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
   plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev
+  plfx::PsrTravList psr_trav_lowered;  // and for plfx_traverse_psr
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -508,7 +512,7 @@ bool env_settings(plfx_ctx *ctx) {
     int v = std::atoi(env);
     if (v > 0) ctx->max_blocks = v;
   }
-  if (const char *env = std::getenv("PLFX_FUSE")) ctx->fuse = std::atoi(env);
+  if (const char *env = std::getenv("PLFX_FUSE")) ctx->fuse = ctx->psr_fuse = std::atoi(env);
   // PLFX_NODE_SEGMENTS: "1" on, "0" off, "-1" / "auto" / unset by size; any
   // other value is refused (a typo must not silently switch the mapping)
   if (const char *env = std::getenv("PLFX_NODE_SEGMENTS")) {
@@ -1126,6 +1130,55 @@ int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int c
                                         ncat, wgt, n, tipvec, w->ws, ctx->max_blocks, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "plf_psr launch");
   }
+  return PLFX_OK;
+}
+
+int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
+                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  for (int &c : ctx->sched) c = 0;
+  if (nops < 0 || (nops > 0 && (!ops || !clv))) return fail(ctx, PLFX_ERR_INVALID, "bad traverse_psr arguments");
+  // plan: levels and level pairs from the op list and the tip slots alone
+  std::vector<unsigned char> tip_mask;
+  if (nops > 0 && tips)
+    for (int sl = 0; sl < nslots; sl++) tip_mask.push_back(tips[sl] != nullptr);
+  plfx::TravPlan plan;
+  std::string err;
+  if (plfx::plan_traversal(ops, nops, nslots, npmats, tip_mask.empty() ? nullptr : tip_mask.data(), 4,
+                           std::min(ctx->psr_fuse, 1), &plan, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  // lower: the call, every op and every level pair checked, every descriptor
+  // filled, before the first launch
+  const plfx::TravArrays arrays{ops, nops, clv, tips, pmats, scalers, scaler_sums};
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat};
+  if (plfx::lower_psr_traversal(plan, arrays, call, &ctx->psr_trav_lowered, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  int sched[PLFX_SCHED_COUNTS] = {};  // [0..3]: passes PSR does not have
+  sched[4] = plan.counts[plfx::kTravTriple];
+  sched[5] = plan.counts[5];
+  hipStream_t s = pick(stream);
+  if (n == 0 || nops == 0) {  // nothing to launch
+    if (int rc = zero_sums(ctx, s, scaler_sums, nops); rc != PLFX_OK) return rc;
+    std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
+    return PLFX_OK;
+  }
+  PLFX_WS(ctx, s, w);
+  const plfx::PsrTravList &l = ctx->psr_trav_lowered;
+  static_assert(3 * plfx::kMaxTriples <= kWsRegions, "three ticket regions per level pair");
+  for (const plfx::PsrTravItem &it : l.items) {
+    const hipError_t e =
+        it.kind == plfx::kPsrTravTriples
+            ? plfx::launch_plf_psr_triples(dtype, it.tips, &l.triples[it.first], it.count, EV, rate_cat, ncat, wgt, n,
+                                           tipvec, w->ws, ctx->max_blocks, s)
+            : plfx::launch_plf_psr(dtype, it.tips, &l.nodes[it.first], it.count, EV, rate_cat, ncat, wgt, n, tipvec,
+                                   w->ws, ctx->max_blocks, s);
+    if (e != hipSuccess)
+      return hip_fail(ctx, e, it.kind == plfx::kPsrTravTriples ? "plf_psr level-pair launch" : "plf_psr launch");
+  }
+  sched[6] = l.launches();
+  std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
   return PLFX_OK;
 }
 

@@ -55,7 +55,7 @@ EXPORTS = (
     "plfx_shard", "plfx_gen_hostmem", "plfx_swemu_instance_run", "plfx_traverse_schedule",
     "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize", "plfx_edge_optimize_dev",
     "plfx_plf_psr_dev", "plfx_root_lnl_psr", "plfx_edge_sumtable_psr", "plfx_edge_derivatives_psr",
-    "plfx_edge_optimize_psr",
+    "plfx_edge_optimize_psr", "plfx_traverse_psr",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -185,6 +185,8 @@ def load():
     L.plfx_edge_derivatives_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.plfx_edge_optimize_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32, dp, dp,
                                          C.POINTER(i32), vp]
+    L.plfx_traverse_psr.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, vp,
+                                    i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
     _lib = L
     return L
 
@@ -813,6 +815,73 @@ class Context:
         self._check(self._L.plfx_plf_psr_dev(
             self.h, F32 if dt == torch.float32 else F64, arr, len(nodes), C.c_void_p(EV.data_ptr()), n,
             C.c_void_p(rate_cat.data_ptr()), ncat, C.c_void_p(p(wgt)), self._tipvec(tipvec, dt), self._sh(stream)))
+
+    def traverse_psr(self, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None, scaler_sums=None,
+                     stream=None, tips=None, tipvec=None, states=4):
+        """A post-order traversal under per-site rate categories (plfx.h
+        section 11, plfx_traverse_psr).  ops, clv, tips, scalers, scaler_sums
+        as traverse(); a CLV slot holds 4*n values; pmats holds whole (left,
+        right) pairs of ncat * 16 values each, as pmatrix() writes them for
+        2*npmats branches and ncat rates; rate_cat, ncat, tipvec as plf_psr().
+        Level pairs are fused only in a context created with PLFX_FUSE >= 1
+        in the environment.  last_schedule() reports the call: triples,
+        unfused, launches."""
+        import torch
+
+        self._psr_states(states)
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
+        nops = ops.shape[0]
+        n, ncat = int(n), int(ncat)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        nslots = len(clv)
+        if tips is not None and len(tips) != nslots:
+            raise PlfxError(ERR_INVALID, "tips must have one entry per slot")
+        for s_, t in enumerate(clv):
+            tip = None if tips is None else tips[s_]
+            if tip is not None:
+                if tip.dtype != torch.uint8 or tip.numel() < n or not tip.is_contiguous() or not tip.is_cuda:
+                    raise PlfxError(ERR_INVALID, f"tip slot {s_}: contiguous uint8 >= n required")
+                continue
+            if t is None or t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda:
+                raise PlfxError(ERR_INVALID, "every CLV slot must be a contiguous device tensor, same dtype, >= 4*n")
+        M = 16 * max(ncat, 1)
+        if pmats.dtype != dt or pmats.numel() % (2 * M):
+            raise PlfxError(ERR_INVALID, f"pmats must hold whole (left, right) pairs of {M} values")
+        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or scaler_sums.numel() < nops
+                                        or not scaler_sums.is_cuda):
+            raise PlfxError(ERR_INVALID, "scaler_sums must be an int64 device tensor with >= nops entries")
+        if scalers is not None:
+            if len(scalers) > nops:
+                raise PlfxError(ERR_INVALID, "more scaler tensors than ops")
+            scalers = list(scalers) + [None] * (nops - len(scalers))
+            for j, t in enumerate(scalers):
+                if t is not None and (t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous()
+                                      or t.numel() < n):
+                    raise PlfxError(ERR_INVALID, f"scaler of op {j} must be a contiguous uint8 "
+                                                 f"device tensor of >= n elements")
+        self._psr_cats(rate_cat, n)
+        _check_aux(n, wgt, None, None)
+        for t in (pmats, EV):
+            if not t.is_cuda or not t.is_contiguous():
+                raise PlfxError(ERR_INVALID, "pmats and EV must be contiguous device tensors")
+        if EV.numel() < 16:
+            raise PlfxError(ERR_INVALID, "EV needs 16 values")
+        top = (TravOp * max(1, nops))(*[TravOp(*map(int, r)) for r in ops])
+        slots = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in clv])
+        tp = None
+        if tips is not None:
+            tp = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in tips])
+        sc = None
+        if scalers is not None:
+            sc = (C.c_void_p * max(1, nops))(*[None if t is None else t.data_ptr() for t in scalers])
+        self._check(self._L.plfx_traverse_psr(
+            self.h, F32 if dt == torch.float32 else F64, top, nops, slots, tp, nslots,
+            C.c_void_p(pmats.data_ptr()), pmats.numel() // (2 * M), C.c_void_p(EV.data_ptr()), n,
+            C.c_void_p(rate_cat.data_ptr()), ncat, C.c_void_p(None if wgt is None else wgt.data_ptr()), sc,
+            C.c_void_p(None if scaler_sums is None else scaler_sums.data_ptr()), self._tipvec(tipvec, dt),
+            self._sh(stream)))
 
     def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
                      stream=None):

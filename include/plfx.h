@@ -358,7 +358,8 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
                        uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
                        void *stream);
 
-/* The schedule the last plfx_traverse(_tips) call on this context chose:
+/* The schedule the last plfx_traverse(_tips) or plfx_traverse_psr call on this
+ * context chose:
  * counts[i] for i < ncounts (extra entries are not written) of
  *   0: fused six-level passes (63 ops)   1: five-level (31)   2: four-level (15)
  *   3: three-level passes (7 ops)        4: level pairs (3 ops)
@@ -635,6 +636,40 @@ typedef struct {
 int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
                      int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
                      void *stream);
+
+/* plfx_traverse_tips for PSR CLVs: a whole post-order op list in one call.
+ * ops, clv, tips, nslots, scalers, scaler_sums as there (a slot with tips[s]
+ * != NULL is a coded tip and may not be a parent; tips NULL = no tips); EV,
+ * rate_cat, ncat, wgt, tipvec and the CLV layout (n * 4 values) as in
+ * plfx_plf_psr_dev.  Op j's matrices are left = pmats + (2*pmat) * ncat*16 and
+ * right = pmats + (2*pmat + 1) * ncat*16 values of dtype: what plfx_pmatrix
+ * writes for 2 * npmats branches and ncat rates.
+ * The ops are levelled as in plfx_traverse_tips; per level, ops a, b whose
+ * outputs are the two children of an op p of the next level (a and b with the
+ * same number of coded children) run with p as one fused level-pair launch
+ * (up to 10 triples each) that never reads a's and b's CLVs back, and the
+ * other ops as plfx_plf_psr_dev batches.  Whatever the schedule, every CLV,
+ * scaler byte and scaler_sums[j] is bit-identical to running the ops one by
+ * one in list order as one-node plfx_plf_psr_dev calls.  Level pairs are
+ * formed when the environment's PLFX_FUSE is >= 1 (deeper fused passes do not
+ * exist for PSR).  PLFX_FUSE=0 or unset runs every op unfused: unlike the
+ * Gamma traversals, fusion is not the default here, because level pairs are
+ * faster on large alignments only (at 2^20 sites, not at 2^14).
+ * plfx_traverse_schedule reports the call: entries 0..3 are 0, 4 the level
+ * pairs, 5 the unfused ops, 6 the launches.
+ * Asynchronous, allocates nothing, descriptors in the kernel arguments,
+ * capture-safe as plfx_plf_psr_dev.  Every check runs before the first launch
+ * (PLFX_ERR_INVALID, nothing is launched): the op list's (slot / pmat range,
+ * a parent that is a child of its op or a tip), ncat, n < 0, a null EV /
+ * rate_cat / pmats / clv, per op the node checks of plfx_plf_psr_dev (a null
+ * CLV of a non-tip slot, alignment, a parent sharing a byte with a child it
+ * reads), and per level pair that none of its three outputs shares a byte
+ * with another of them or with one of its four leaves.  n == 0 or nops == 0:
+ * nothing is launched and scaler_sums[0..nops) is zeroed. */
+int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
+                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream);
 
 /* lnL = sum_i wgt_i * log( sum_s freq[s] * x[i][s] )
  *       + (sum_{j<nsums} scaler_sums[j]) * log(2^-32)

@@ -18,7 +18,15 @@
 # 256 MB Infinity Cache, which replays of one graph can hit; `--big` adds the
 # dense/dense PSR rows at 2^23 sites (805 MB in f64), beyond it.
 #
+# `--tree` measures a whole traversal instead, the same way: the balanced
+# 64-taxon tree with coded tips, ncat 25, f64 and f32, at 2^14 and 2^20 sites,
+# by three routes -- (i) the caller's own level-by-level plfx_plf_psr_dev
+# batches, (ii) plfx_traverse_psr under PLFX_FUSE=0, (iii) plfx_traverse_psr
+# under PLFX_FUSE=1 (fused level pairs).  A library without plfx_traverse_psr
+# gets row (i) alone: that run is the baseline of the other two.
+#
 #   python tools/psr_bench.py [--calls 200] [--rounds 7] [--sites N] [--big]
+#   python tools/psr_bench.py --tree [--calls 200] [--rounds 7]
 import argparse
 import statistics
 import sys
@@ -114,15 +122,115 @@ def report(label, n, rows, res):
               f"{nbytes / n:6.1f} B/site {gbs:7.1f} GB/s {gbs / HBM_PEAK_GBS:.3f} of HBM peak", flush=True)
 
 
+TREE_TAXA = 64
+# CLV streams (4 values per site each) of the balanced 64-taxon tree with coded
+# tips: node by node 32 + 48 + 24 + 12 + 6 + 3, with fused level pairs 48 + 28 + 7
+TREE_STREAMS = {"unfused": 125, "fused": 83}
+
+
+def tree_rows(ctxs, dt, n):
+    """{name: (call(stream), algorithmic bytes)} of one traversal of the balanced
+    64-taxon tree with coded tips, ncat 25, n sites: (i) the caller's own
+    level-by-level plf_psr batches, (ii) traverse_psr on a PLFX_FUSE=0 context,
+    (iii) traverse_psr on a PLFX_FUSE=1 context (level pairs fused).  (ii) and
+    (iii) only where the library has plfx_traverse_psr, so the tool also runs
+    on a build without it."""
+    es = 8 if dt == torch.float64 else 4
+    gen = torch.Generator(device="cuda").manual_seed(n % 1000 + es)
+    rnd = lambda m: torch.rand(m, dtype=dt, device="cuda", generator=gen) * 0.9 + 0.1  # noqa: E731
+    T = TREE_TAXA
+    ops, level, nxt = [], [], T  # slots 0..T-1 the tips; level by level, pmat = the op's index
+    cur = list(range(T))
+    lv = 0
+    while len(cur) > 1:
+        up = []
+        for i in range(0, len(cur), 2):
+            ops.append((nxt, cur[i], cur[i + 1], len(ops)))
+            level.append(lv)
+            up.append(nxt)
+            nxt += 1
+        cur, lv = up, lv + 1
+    nops, M = len(ops), 16 * NCAT
+    tips = [torch.randint(1, 16, (n,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(T)] + [None] * nops
+    clv = [None] * T + [torch.empty(4 * n, dtype=dt, device="cuda") for _ in range(nops)]
+    EV, pmats = rnd(16) * 0.3, rnd(2 * nops * M)
+    cat = torch.randint(0, NCAT, (n,), dtype=torch.uint8, device="cuda", generator=gen)
+    wgt = torch.ones(n, dtype=torch.int32, device="cuda")
+    sc = [torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(nops)]
+    ss = torch.zeros(nops, dtype=torch.int64, device="cuda")
+    by_level = []
+    for l in range(lv):
+        nodes = []
+        for j, (p, a, b, pm) in enumerate(ops):
+            if level[j] != l:
+                continue
+            nd = dict(x3=clv[p], left=pmats[2 * pm * M:(2 * pm + 1) * M], right=pmats[(2 * pm + 1) * M:(2 * pm + 2) * M],
+                      scaler=sc[j], scaler_sum=ss[j:j + 1])
+            nd.update(dict(tip1=tips[a], tip2=tips[b]) if l == 0 else dict(x1=clv[a], x2=clv[b]))
+            nodes.append(nd)
+        by_level.append(nodes)
+    aops = np.array(ops, np.int32)
+
+    def own_levels(s, c=ctxs["fuse0"]):
+        for nodes in by_level:
+            c.plf_psr(nodes, EV, n, cat, NCAT, wgt=wgt, stream=s)
+
+    def traverse(c):
+        return lambda s: c.traverse_psr(aops, clv, pmats, EV, n, cat, NCAT, wgt=wgt, scalers=sc, scaler_sums=ss,
+                                        stream=s, tips=tips)
+
+    # per site: the CLV streams, the tip codes, and per op the category, the weight and the scaler byte
+    nbytes = lambda streams, passes: n * (streams * 4 * es + T + passes * 5 + nops)  # noqa: E731
+    rows = {"(i) plf_psr level by level": (own_levels, nbytes(TREE_STREAMS["unfused"], nops))}
+    if hasattr(ctxs["fuse1"], "traverse_psr"):
+        rows["(ii) traverse_psr PLFX_FUSE=0"] = (traverse(ctxs["fuse0"]), nbytes(TREE_STREAMS["unfused"], nops))
+        rows["(iii) traverse_psr PLFX_FUSE=1"] = (traverse(ctxs["fuse1"]), nbytes(TREE_STREAMS["fused"], nops // 3))
+    return rows
+
+
+def tree_main(a):
+    """--tree: the three routes at 2^14 and 2^20 sites, f64 and f32."""
+    import os
+
+    ctxs, old = {}, os.environ.get("PLFX_FUSE")
+    for k, v in (("fuse0", "0"), ("fuse1", "1")):  # read when a context is created
+        os.environ["PLFX_FUSE"] = v
+        ctxs[k] = plfx.Context(0, lazy_tables=True)
+    if old is None:
+        del os.environ["PLFX_FUSE"]
+    else:
+        os.environ["PLFX_FUSE"] = old
+    for dt, label in ((torch.float64, "f64"), (torch.float32, "f32")):
+        for n in (1 << 14, 1 << 20):
+            rows = tree_rows(ctxs, dt, n)
+            res = measure(ctxs["fuse0"], rows, a.calls, a.rounds)
+            report(f"tree64 {label}", n, rows, res)
+            if "(iii) traverse_psr PLFX_FUSE=1" in rows:
+                print(f"tree64 {label} n={n} schedule: PLFX_FUSE=1 {ctxs['fuse1'].last_schedule()} "
+                      f"PLFX_FUSE=0 {ctxs['fuse0'].last_schedule()}", flush=True)
+                own = res["(i) plf_psr level by level"]
+                for k in ("(ii) traverse_psr PLFX_FUSE=0", "(iii) traverse_psr PLFX_FUSE=1"):
+                    print(f"tree64 {label} n={n} {k} time / (i) time = {res[k][0] / own[0]:.3f} "
+                          f"(medians; (i) rounds span {own[1]:.2f}..{own[2]:.2f} us)", flush=True)
+            del rows
+            torch.cuda.empty_cache()
+    for c in ctxs.values():
+        c.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--sites", type=int, default=1 << 20)
     ap.add_argument("--big", action="store_true", help="add the dense/dense PSR rows at 2^23 sites")
+    ap.add_argument("--tree", action="store_true",
+                    help="instead: one traversal of the balanced 64-taxon coded-tip tree, three routes, 2^14 and 2^20 sites")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("psr_bench needs a GPU")
+    if a.tree:
+        return tree_main(a)
     ctx = plfx.Context(0, lazy_tables=True)
     for dt, label in ((torch.float64, "f64"), (torch.float32, "f32")):
         n = a.sites
