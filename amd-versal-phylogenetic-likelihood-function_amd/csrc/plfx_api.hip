@@ -20,7 +20,6 @@
 #include "edge_newton.hpp"
 #include "plf_kernels.hpp"
 #include "psr_lower.hpp"
-#include "psr_trav_lower.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
 #include "trav_lower.hpp"
@@ -60,8 +59,7 @@ struct plfx_ctx {
   double *edge_buf = nullptr;       // plfx_edge_optimize: the trial t and the three results (kEdgeBufBytes)
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
   plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
-  plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev
-  plfx::PsrTravList psr_trav_lowered;  // and for plfx_traverse_psr
+  plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev and plfx_traverse_psr
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -286,6 +284,14 @@ int zero_sums(plfx_ctx *ctx, hipStream_t s, void *sums, int count) {
   return PLFX_OK;
 }
 
+// n == 0 for a batch of nodes: the sum of each (may be NULL) is zero
+template <typename Node>
+int zero_node_sums(plfx_ctx *ctx, hipStream_t s, const Node *nodes, int count) {
+  for (int i = 0; i < count; i++)
+    if (int rc = zero_sums(ctx, s, nodes[i].scaler_sum, 1); rc != PLFX_OK) return rc;
+  return PLFX_OK;
+}
+
 // one DNA node of dtype (PLFX_F32 / PLFX_F64, checked by the caller)
 int plf_dev(plfx_ctx *ctx, int dtype, const void *x1, const void *x2, void *x3, const void *EV, int64_t n,
             const void *left, const void *right, const int32_t *wgt, uint8_t *scaler,
@@ -488,11 +494,7 @@ int execute(plfx_ctx *ctx, const plfx::LaunchList &l, const ExecCall &c, unsigne
 int run_batch(plfx_ctx *ctx, const ExecCall &c, const plfx_node *nodes, int count, int tips) {
   if (count < 0 || c.n < 0 || (count > 0 && (!nodes || !c.EV)))
     return fail(ctx, PLFX_ERR_INVALID, "bad batch arguments");
-  if (c.n == 0) {
-    for (int i = 0; i < count; i++)
-      if (int rc = zero_sums(ctx, c.s, nodes[i].scaler_sum, 1); rc != PLFX_OK) return rc;
-    return PLFX_OK;
-  }
+  if (c.n == 0) return zero_node_sums(ctx, c.s, nodes, count);
   if (count == 0) return PLFX_OK;
   PLFX_WS(ctx, c.s, w);
   if (c.states == 20 && tips == 2)
@@ -502,6 +504,73 @@ int run_batch(plfx_ctx *ctx, const ExecCall &c, const plfx_node *nodes, int coun
   if (plfx::lower_batch(lc, nodes, count, tips, nullptr, &ctx->lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   return execute(ctx, ctx->lowered, c, w->ws);
+}
+
+// The launches of a lowered per-site-rate call (psr_lower.hpp), in list order.
+int execute_psr(plfx_ctx *ctx, const plfx::PsrLaunchList &l, const plfx::PsrCall &c, const int32_t *wgt,
+                const void *tipvec, hipStream_t s, unsigned long long *ws) {
+  static_assert(3 * plfx::kMaxTriples <= kWsRegions, "three ticket regions per level pair");
+  for (const plfx::PsrLaunch &it : l.items) {
+    const bool triples = it.kind == plfx::kPsrTriples;
+    const hipError_t e =
+        triples ? plfx::launch_plf_psr_triples(c.dtype, it.tips, &l.triples[it.first], it.count, c.EV, c.rate_cat,
+                                               c.ncat, wgt, c.n, tipvec, ws, ctx->max_blocks, s)
+                : plfx::launch_plf_psr(c.dtype, it.tips, &l.nodes[it.first], it.count, c.EV, c.rate_cat, c.ncat, wgt,
+                                       c.n, tipvec, ws, ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, triples ? "plf_psr level-pair launch" : "plf_psr launch");
+  }
+  return PLFX_OK;
+}
+
+// The plan of a traversal call: levels and fused groups from the op list and
+// the tip slots alone.
+int plan_call(plfx_ctx *ctx, const plfx_trav_op *ops, int nops, const uint8_t *const *tips, int nslots, int npmats,
+              int states, int fuse, plfx::TravPlan *plan) {
+  std::vector<unsigned char> tip_mask;
+  if (nops > 0 && tips)
+    for (int sl = 0; sl < nslots; sl++) tip_mask.push_back(tips[sl] != nullptr);
+  std::string err;
+  if (plfx::plan_traversal(ops, nops, nslots, npmats, tip_mask.empty() ? nullptr : tip_mask.data(), states, fuse,
+                           plan, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  return PLFX_OK;
+}
+
+// The end of a traversal call that was not refused: its schedule as
+// plfx_traverse_schedule reports it from now on (launches 0: nothing to launch).
+int publish_sched(plfx_ctx *ctx, const plfx::TravPlan &plan, int launches) {
+  static_assert(PLFX_SCHED_COUNTS == 7, "the plan's six counts, then the launches");
+  std::copy(plan.counts, plan.counts + 6, ctx->sched);
+  ctx->sched[6] = launches;
+  return PLFX_OK;
+}
+
+// The arguments of plfx_edge_sumtable and plfx_edge_sumtable_psr after dtype
+// and states; clv_bytes of one CLV of the call.  n == 0 passes: the caller
+// returns then.
+int check_sumtable_args(plfx_ctx *ctx, const uint8_t *tip1, const void *x1, const void *x2, int64_t n,
+                        const void *tipvec, const void *sumtab, size_t clv_bytes) {
+  if ((tip1 != nullptr) == (x1 != nullptr))
+    return fail(ctx, PLFX_ERR_INVALID, "side 1 needs exactly one of tip / CLV");
+  if (tip1 && !tipvec)
+    return fail(ctx, PLFX_ERR_INVALID, "a coded side needs tipvec (the default 0/1 table is not in eigen coordinates)");
+  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
+  if (n == 0) return PLFX_OK;
+  if (!x2 || !sumtab) return fail(ctx, PLFX_ERR_INVALID, "null CLV / sum table pointer");
+  if ((x1 && !aligned16(x1)) || !aligned16(x2) || !aligned16(sumtab))
+    return fail(ctx, PLFX_ERR_INVALID, "CLV pointers must be 16-byte aligned");
+  if (overlap(sumtab, clv_bytes, tip1 ? (const void *)tip1 : x1, tip1 ? (size_t)n : clv_bytes) ||
+      overlap(sumtab, clv_bytes, x2, clv_bytes))
+    return fail(ctx, PLFX_ERR_INVALID, "sumtab may not overlap x1/x2");
+  return PLFX_OK;
+}
+
+// What the root-lnL and edge-derivative entry points (`who`) check last:
+// `required` -- their own pointers and sizes -- and the scaler sums.
+int check_sums_args(plfx_ctx *ctx, const char *who, bool required, const int64_t *scaler_sums, int nsums) {
+  if (!required || nsums < 0 || (nsums > 0 && !scaler_sums))
+    return fail(ctx, PLFX_ERR_INVALID, "bad %s arguments", who);
+  return PLFX_OK;
 }
 
 // The environment's settings of a new context; false for a value that is refused.
@@ -888,15 +957,11 @@ int plfx_plf_tips_dev_gen(plfx_ctx *ctx, int dtype, int states, int flags, const
   if (flags & ~PLFX_FMA) return fail(ctx, PLFX_ERR_INVALID, "bad flags %d", flags);
   if ((tip1 != nullptr) == (x1 != nullptr) || (tip2 != nullptr) == (x2 != nullptr))
     return fail(ctx, PLFX_ERR_INVALID, "each child needs exactly one of tip / CLV");
-  plfx_node nd{tip1 ? (const void *)tip1 : x1, tip2 ? (const void *)tip2 : x2, x3, left, right,
-               scaler, scaler_sum};
-  int tips = (tip1 ? 1 : 0) + (tip2 ? 1 : 0);
-  if (!tip1 && tip2) {  // dense/tip runs as tip/dense: u1*u2 == u2*u1 exactly
-    std::swap(nd.x1, nd.x2);
-    std::swap(nd.left, nd.right);
-  }
+  // dense/tip runs as tip/dense: u1*u2 == u2*u1 exactly
+  const plfx::OpNode o = plfx::tip_first({{tip1 ? (const void *)tip1 : x1, tip2 ? (const void *)tip2 : x2, x3, left,
+                                           right, scaler, scaler_sum}, tip1 != nullptr, tip2 != nullptr});
   const ExecCall call{dtype, states, flags, EV, n, wgt, tipvec, pick(stream), /*streams*/ 1};
-  return run_batch(ctx, call, &nd, 1, tips);
+  return run_batch(ctx, call, &o.nd, 1, o.t1 + o.t2);
 }
 
 int plfx_plf_tips_dev(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1,
@@ -930,23 +995,12 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   if (nops < 0 || (nops > 0 && (!ops || !clv || !pmats || !EV)))
     return fail(ctx, PLFX_ERR_INVALID, "bad traverse arguments");
   if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
-  // plan: levels and fused groups from the op list and the tip slots alone
-  std::vector<unsigned char> tip_mask;
-  if (nops > 0 && tips)
-    for (int sl = 0; sl < nslots; sl++) tip_mask.push_back(tips[sl] != nullptr);
   plfx::TravPlan plan;
-  std::string plan_err;
-  if (plfx::plan_traversal(ops, nops, nslots, npmats, tip_mask.empty() ? nullptr : tip_mask.data(),
-                           states, ctx->fuse, &plan, &plan_err) != PLFX_OK)
-    return fail(ctx, PLFX_ERR_INVALID, "%s", plan_err.c_str());
-  int sched[PLFX_SCHED_COUNTS] = {};  // as plfx_traverse_schedule reports it; [6]: launches
-  std::copy(plan.counts, plan.counts + 6, sched);
+  if (int rc = plan_call(ctx, ops, nops, tips, nslots, npmats, states, ctx->fuse, &plan); rc != PLFX_OK) return rc;
   hipStream_t s = pick(stream);
   if (n == 0 || nops == 0) {  // nothing to launch
     const int rc = zero_sums(ctx, s, scaler_sums, nops);
-    if (rc != PLFX_OK) return rc;
-    std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
-    return PLFX_OK;
+    return rc != PLFX_OK ? rc : publish_sched(ctx, plan, 0);
   }
   // lower: every node checked, every descriptor filled, before the first launch
   PLFX_WS(ctx, s, w);
@@ -954,14 +1008,13 @@ int plfx_traverse_tips(plfx_ctx *ctx, int dtype, int states, int flags, const pl
   if (plfx::traversal_uses_tables(arrays, states))
     if (int rc = ensure_tables(ctx, w, s); rc != PLFX_OK) return rc;
   const plfx::LowerCall lc{dtype, states, n, w->tt, ctx->tt_codes};
-  if (plfx::lower_traversal(plan, arrays, lc, &ctx->lowered, &plan_err) != PLFX_OK)
-    return fail(ctx, PLFX_ERR_INVALID, "%s", plan_err.c_str());
+  std::string err;
+  if (plfx::lower_traversal(plan, arrays, lc, &ctx->lowered, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   // execute: level by level, the level's fused groups first
   const ExecCall call{dtype, states, flags, EV, n, wgt, tipvec, s, /*streams*/ 1};
   if (int rc = execute(ctx, ctx->lowered, call, w->ws); rc != PLFX_OK) return rc;
-  sched[6] = ctx->lowered.launches();
-  std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
-  return PLFX_OK;
+  return publish_sched(ctx, plan, ctx->lowered.launches());
 }
 
 int plfx_traverse_schedule(const plfx_ctx *ctx, int *counts, int ncounts) {
@@ -979,8 +1032,8 @@ int plfx_root_lnl(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n
   PLFX_BIND(ctx);
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (states != 4 && states != 20) return fail(ctx, PLFX_ERR_UNSUPPORTED, "lnl: states=%d", states);
-  if (!out_lnl || n < 0 || (n > 0 && !x) || nsums < 0 || (nsums > 0 && !scaler_sums))
-    return fail(ctx, PLFX_ERR_INVALID, "bad root_lnl arguments");
+  if (int rc = check_sums_args(ctx, "root_lnl", out_lnl && n >= 0 && (n == 0 || x), scaler_sums, nsums); rc != PLFX_OK)
+    return rc;
   hipStream_t s = pick(stream);
   if (n == 0) {
     const int rc = zero_sums(ctx, s, out_lnl, 1);
@@ -1028,18 +1081,8 @@ int plfx_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (states != 4 && states != 20)
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "edge_sumtable: states=%d not built (4, 20)", states);
-  if ((tip1 != nullptr) == (x1 != nullptr))
-    return fail(ctx, PLFX_ERR_INVALID, "side 1 needs exactly one of tip / CLV");
-  if (tip1 && !tipvec)
-    return fail(ctx, PLFX_ERR_INVALID, "a coded side needs tipvec (the default 0/1 table is not in eigen coordinates)");
-  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
-  if (n == 0) return PLFX_OK;
-  if (!x2 || !sumtab) return fail(ctx, PLFX_ERR_INVALID, "null CLV / sum table pointer");
-  if ((x1 && !aligned16(x1)) || !aligned16(x2) || !aligned16(sumtab))
-    return fail(ctx, PLFX_ERR_INVALID, "CLV pointers must be 16-byte aligned");
-  const size_t cb = clv_bytes_of(dtype, states, n);
-  if (overlap(sumtab, cb, tip1 ? (const void *)tip1 : x1, tip1 ? (size_t)n : cb) || overlap(sumtab, cb, x2, cb))
-    return fail(ctx, PLFX_ERR_INVALID, "sumtab may not overlap x1/x2");
+  const int rc = check_sumtable_args(ctx, tip1, x1, x2, n, tipvec, sumtab, clv_bytes_of(dtype, states, n));
+  if (rc != PLFX_OK || n == 0) return rc;
   hipError_t e = plfx::launch_edge_sumtable(dtype, states, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2,
                                             n, tipvec, sumtab, ctx->max_blocks, pick(stream));
   if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable launch");
@@ -1052,8 +1095,7 @@ int plfx_edge_derivatives(plfx_ctx *ctx, int dtype, int states, const void *sumt
                           double *out3, double *site_lnl, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_edge_args(ctx, dtype, states, sumtab, n, eigen, rates, ncat); rc != PLFX_OK) return rc;
-  if (!t || !out3 || nsums < 0 || (nsums > 0 && !scaler_sums))
-    return fail(ctx, PLFX_ERR_INVALID, "bad edge_derivatives arguments");
+  if (int rc = check_sums_args(ctx, "edge_derivatives", t && out3, scaler_sums, nsums); rc != PLFX_OK) return rc;
   hipStream_t s = pick(stream);
   PLFX_WS(ctx, s, w);
   // n == 0 launches too: one block, out3 = {correction, 0, 0}
@@ -1119,18 +1161,9 @@ int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int c
   if (plfx::lower_psr(call, nodes, count, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   hipStream_t s = pick(stream);
-  if (n == 0) {
-    for (int i = 0; i < count; i++)
-      if (int rc = zero_sums(ctx, s, nodes[i].scaler_sum, 1); rc != PLFX_OK) return rc;
-    return PLFX_OK;
-  }
+  if (n == 0) return zero_node_sums(ctx, s, nodes, count);
   PLFX_WS(ctx, s, w);
-  for (const plfx::PsrLaunch &it : ctx->psr_lowered.items) {
-    hipError_t e = plfx::launch_plf_psr(dtype, it.tips, &ctx->psr_lowered.nodes[it.first], it.count, EV, rate_cat,
-                                        ncat, wgt, n, tipvec, w->ws, ctx->max_blocks, s);
-    if (e != hipSuccess) return hip_fail(ctx, e, "plf_psr launch");
-  }
-  return PLFX_OK;
+  return execute_psr(ctx, ctx->psr_lowered, call, wgt, tipvec, s, w->ws);
 }
 
 int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
@@ -1140,46 +1173,25 @@ int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nop
   PLFX_BIND(ctx);
   for (int &c : ctx->sched) c = 0;
   if (nops < 0 || (nops > 0 && (!ops || !clv))) return fail(ctx, PLFX_ERR_INVALID, "bad traverse_psr arguments");
-  // plan: levels and level pairs from the op list and the tip slots alone
-  std::vector<unsigned char> tip_mask;
-  if (nops > 0 && tips)
-    for (int sl = 0; sl < nslots; sl++) tip_mask.push_back(tips[sl] != nullptr);
+  // level pairs alone: the deeper passes of entries 0..3 of the schedule are not built for PSR
   plfx::TravPlan plan;
-  std::string err;
-  if (plfx::plan_traversal(ops, nops, nslots, npmats, tip_mask.empty() ? nullptr : tip_mask.data(), 4,
-                           std::min(ctx->psr_fuse, 1), &plan, &err) != PLFX_OK)
-    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  if (int rc = plan_call(ctx, ops, nops, tips, nslots, npmats, 4, std::min(ctx->psr_fuse, 1), &plan); rc != PLFX_OK)
+    return rc;
   // lower: the call, every op and every level pair checked, every descriptor
   // filled, before the first launch
   const plfx::TravArrays arrays{ops, nops, clv, tips, pmats, scalers, scaler_sums};
   const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat};
-  if (plfx::lower_psr_traversal(plan, arrays, call, &ctx->psr_trav_lowered, &err) != PLFX_OK)
+  std::string err;
+  if (plfx::lower_psr_traversal(plan, arrays, call, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
-  int sched[PLFX_SCHED_COUNTS] = {};  // [0..3]: passes PSR does not have
-  sched[4] = plan.counts[plfx::kTravTriple];
-  sched[5] = plan.counts[5];
   hipStream_t s = pick(stream);
   if (n == 0 || nops == 0) {  // nothing to launch
-    if (int rc = zero_sums(ctx, s, scaler_sums, nops); rc != PLFX_OK) return rc;
-    std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
-    return PLFX_OK;
+    const int rc = zero_sums(ctx, s, scaler_sums, nops);
+    return rc != PLFX_OK ? rc : publish_sched(ctx, plan, 0);
   }
   PLFX_WS(ctx, s, w);
-  const plfx::PsrTravList &l = ctx->psr_trav_lowered;
-  static_assert(3 * plfx::kMaxTriples <= kWsRegions, "three ticket regions per level pair");
-  for (const plfx::PsrTravItem &it : l.items) {
-    const hipError_t e =
-        it.kind == plfx::kPsrTravTriples
-            ? plfx::launch_plf_psr_triples(dtype, it.tips, &l.triples[it.first], it.count, EV, rate_cat, ncat, wgt, n,
-                                           tipvec, w->ws, ctx->max_blocks, s)
-            : plfx::launch_plf_psr(dtype, it.tips, &l.nodes[it.first], it.count, EV, rate_cat, ncat, wgt, n, tipvec,
-                                   w->ws, ctx->max_blocks, s);
-    if (e != hipSuccess)
-      return hip_fail(ctx, e, it.kind == plfx::kPsrTravTriples ? "plf_psr level-pair launch" : "plf_psr launch");
-  }
-  sched[6] = l.launches();
-  std::copy(sched, sched + PLFX_SCHED_COUNTS, ctx->sched);
-  return PLFX_OK;
+  if (int rc = execute_psr(ctx, ctx->psr_lowered, call, wgt, tipvec, s, w->ws); rc != PLFX_OK) return rc;
+  return publish_sched(ctx, plan, ctx->psr_lowered.launches());
 }
 
 int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
@@ -1187,8 +1199,9 @@ int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const 
                       double *site_lnl, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
-  if (!out_lnl || n < 0 || (n > 0 && !x) || nsums < 0 || (nsums > 0 && !scaler_sums))
-    return fail(ctx, PLFX_ERR_INVALID, "bad root_lnl_psr arguments");
+  if (int rc = check_sums_args(ctx, "root_lnl_psr", out_lnl && n >= 0 && (n == 0 || x), scaler_sums, nsums);
+      rc != PLFX_OK)
+    return rc;
   if (!aligned16(x)) return fail(ctx, PLFX_ERR_INVALID, "the CLV must be 16-byte aligned");
   hipStream_t s = pick(stream);
   if (n == 0) {
@@ -1206,18 +1219,8 @@ int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const 
                            int64_t n, const void *tipvec, void *sumtab, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
-  if ((tip1 != nullptr) == (x1 != nullptr))
-    return fail(ctx, PLFX_ERR_INVALID, "side 1 needs exactly one of tip / CLV");
-  if (tip1 && !tipvec)
-    return fail(ctx, PLFX_ERR_INVALID, "a coded side needs tipvec (the default 0/1 table is not in eigen coordinates)");
-  if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%lld)", (long long)n);
-  if (n == 0) return PLFX_OK;
-  if (!x2 || !sumtab) return fail(ctx, PLFX_ERR_INVALID, "null CLV / sum table pointer");
-  if ((x1 && !aligned16(x1)) || !aligned16(x2) || !aligned16(sumtab))
-    return fail(ctx, PLFX_ERR_INVALID, "CLV pointers must be 16-byte aligned");
-  const size_t cb = plfx::psr_clv_bytes(dtype, n);
-  if (overlap(sumtab, cb, tip1 ? (const void *)tip1 : x1, tip1 ? (size_t)n : cb) || overlap(sumtab, cb, x2, cb))
-    return fail(ctx, PLFX_ERR_INVALID, "sumtab may not overlap x1/x2");
+  const int rc = check_sumtable_args(ctx, tip1, x1, x2, n, tipvec, sumtab, plfx::psr_clv_bytes(dtype, n));
+  if (rc != PLFX_OK || n == 0) return rc;
   hipError_t e = plfx::launch_edge_sumtable_psr(dtype, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2, n,
                                                 tipvec, sumtab, ctx->max_blocks, pick(stream));
   if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr launch");
@@ -1230,8 +1233,7 @@ int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int6
                               double *site_lnl, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
-  if (!t || !out3 || nsums < 0 || (nsums > 0 && !scaler_sums))
-    return fail(ctx, PLFX_ERR_INVALID, "bad edge_derivatives_psr arguments");
+  if (int rc = check_sums_args(ctx, "edge_derivatives_psr", t && out3, scaler_sums, nsums); rc != PLFX_OK) return rc;
   hipStream_t s = pick(stream);
   PLFX_WS(ctx, s, w);
   // n == 0 launches too: one block, out3 = {correction, 0, 0}

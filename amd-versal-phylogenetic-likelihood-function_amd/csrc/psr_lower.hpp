@@ -1,14 +1,18 @@
-// psr_lower.hpp -- from the nodes of a plfx_plf_psr_dev call to the list of
-// kernel launches the C ABI issues: the call's and every node's checks, the
-// descriptors, and the split into launches of one kind of children and at
-// most kMaxBatch nodes.  Plain C++: device pointers are stored and compared,
-// never followed (tests/psr_lower_main.cpp drives it on the CPU).
+// psr_lower.hpp -- from the nodes of a plfx_plf_psr_dev call, or a traversal
+// plan (trav_plan.hpp) and the arrays of a plfx_traverse_psr call, to the list
+// of kernel launches the C ABI issues: the call's, every node's and every
+// fused group's checks, the descriptors, and the split into launches of one
+// kind of children.  Plain C++: device pointers are stored and compared, never
+// followed (tests/psr_lower_main.cpp and tests/psr_trav_lower_main.cpp drive
+// it on the CPU).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "../../include/plfx.h"
 #include "plf_desc.hpp"
+#include "trav_lower.hpp"  // TravArrays
+#include "trav_plan.hpp"
 
 namespace plfx {
 
@@ -21,10 +25,18 @@ struct PsrCall {
   const uint8_t *rate_cat;
 };
 
-// One kernel launch: nodes[first, first + count), count <= kMaxBatch, all with
-// the same kind of children -- tips bit 0: child 1 is coded, bit 1: child 2
-// (a coded child's descriptor pointer names its uint8 codes).
+enum PsrLaunchKind {
+  kPsrNodes,    // nodes[first, first + count): count <= kMaxBatch
+  kPsrTriples,  // triples[first, first + count): count <= kMaxTriples
+};
+
+// One kernel launch.  Nodes: all with the same kind of children -- tips bit 0:
+// child 1 is coded, bit 1: child 2.  Triples: tips = the number of coded
+// children of each leaf op (0, 1, 2), coded child first.  A coded child's
+// descriptor pointer names its uint8 codes.
 struct PsrLaunch {
+  int kind;   // PsrLaunchKind
+  int level;  // of the traversal (0 for a plain batch)
   int tips;
   int first, count;
 };
@@ -32,10 +44,13 @@ struct PsrLaunch {
 struct PsrLaunchList {
   std::vector<PsrLaunch> items;
   std::vector<NodeDescH> nodes;
+  std::vector<TripleDescH> triples;
   void clear() {  // keeps the capacity: a context lowers every call into one list
     items.clear();
     nodes.clear();
+    triples.clear();
   }
+  int launches() const { return (int)items.size(); }  // plfx_traverse_schedule's entry 6
 };
 
 // bytes of one PSR CLV: n sites * 4 states * element size
@@ -50,5 +65,17 @@ inline size_t psr_clv_bytes(int dtype, int64_t n) {
 // alone, as the Gamma entry points do.  Returns PLFX_OK, or PLFX_ERR_INVALID
 // with *err set and *out empty: nothing of a refused call is launched.
 int lower_psr(const PsrCall &call, const plfx_psr_node *nodes, int count, PsrLaunchList *out, std::string *err);
+
+// The whole traversal, level by level.  Within a level: its triples by tip
+// kind 0, 1, 2 in launches of at most kMaxTriples, then its unfused ops by
+// kind of children as lower_psr.  Op j's matrices are pmats + (2 * pmat) *
+// ncat * 16 and + (2 * pmat + 1) * ncat * 16 values.  A triple's leaf ops are
+// stored coded child first (tip_first); P's children keep the order op P
+// names them in.  Checks, all before the list holds anything: the call's
+// (n == 0 gives an empty list here), every op's section-11 node checks, and
+// per triple that none of its three outputs shares a byte with another of
+// them or with one of its four leaves.  Refusals as lower_psr.
+int lower_psr_traversal(const TravPlan &plan, const TravArrays &t, const PsrCall &call, PsrLaunchList *out,
+                        std::string *err);
 
 }  // namespace plfx

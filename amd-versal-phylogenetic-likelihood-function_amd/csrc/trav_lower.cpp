@@ -30,8 +30,6 @@ int check_node(const plfx_node &d, int tips, int64_t n, int i, size_t clv_bytes,
   return PLFX_OK;
 }
 
-NodeDescH desc(const plfx_node &d) { return NodeDescH{d.x1, d.x2, d.x3, d.left, d.right, d.scaler, d.scaler_sum}; }
-
 void add(LaunchList *out, int kind, int level, int tips, int depth, size_t first, int count) {
   out->items.push_back(LaunchItem{kind, level, tips, depth, (int)first, count});
 }
@@ -83,7 +81,7 @@ void batch(const LowerCall &call, const plfx_node *nodes, int count, int tips, i
     for (int j = 0; j < count; j += kMaxBatch)
       add(out, count == 1 ? kLaunchProtNode : kLaunchProtBatch, level, tips, 0, out->nodes.size() + j,
           std::min(count - j, kMaxBatch));
-    for (int i = 0; i < count; i++) out->nodes.push_back(desc(nodes[i]));
+    for (int i = 0; i < count; i++) out->nodes.push_back(node_desc(nodes[i]));
     return;
   }
   // More than kMaxBatch nodes: launch j takes nodes j, j + L, j + 2L, ... (L
@@ -96,7 +94,7 @@ void batch(const LowerCall &call, const plfx_node *nodes, int count, int tips, i
   const int L = (count + kMaxBatch - 1) / kMaxBatch;
   for (int j = 0; j < L; j++) {
     const size_t first = out->nodes.size();
-    for (int i = j; i < count; i += L) out->nodes.push_back(desc(nodes[i]));
+    for (int i = j; i < count; i += L) out->nodes.push_back(node_desc(nodes[i]));
     add(out, kLaunchDnaBatch, level, tips, 0, first, (int)(out->nodes.size() - first));
   }
 }
@@ -119,19 +117,9 @@ struct TravNodes {
   // the node descriptor of op j, tip child first (dense/tip runs as tip/dense:
   // the product u1*u2 commutes exactly); *kind = number of tip children
   plfx_node node(int j, int *kind) const {
-    const plfx_trav_op &o = t.ops[j];
-    const char *pmats = static_cast<const char *>(t.pmats);
-    const bool t1 = t.tips && t.tips[o.child1], t2 = t.tips && t.tips[o.child2];
-    plfx_node nd{t1 ? (const void *)t.tips[o.child1] : t.clv[o.child1],
-                 t2 ? (const void *)t.tips[o.child2] : t.clv[o.child2], t.clv[o.parent],
-                 pmats + (size_t)(2 * o.pmat) * mat_bytes, pmats + (size_t)(2 * o.pmat + 1) * mat_bytes,
-                 t.scalers ? t.scalers[j] : nullptr, t.scaler_sums ? t.scaler_sums + j : nullptr};
-    if (!t1 && t2) {
-      std::swap(nd.x1, nd.x2);
-      std::swap(nd.left, nd.right);
-    }
-    *kind = (t1 ? 1 : 0) + (t2 ? 1 : 0);
-    return nd;
+    const OpNode o = tip_first(op_node(t, mat_bytes, j));
+    *kind = o.t1 + o.t2;
+    return o.nd;
   }
 };
 
@@ -202,11 +190,7 @@ int lower_levels(const TravPlan &plan, const TravArrays &t, const LowerCall &cal
         // P's children as op P names them: child1 = A's slot or B's slot
         const bool a_first = t.ops[p].child1 == t.ops[a].parent;
         const plfx_node &F = a_first ? A : B, &G = a_first ? B : A;
-        tb[g.tips].push_back(TripleDescH{
-            F.x1, F.x2, G.x1, G.x2, F.x3, G.x3, P.x3, (const double *)F.left,
-            (const double *)F.right, (const double *)G.left, (const double *)G.right,
-            (const double *)P.left, (const double *)P.right, F.scaler, G.scaler, P.scaler,
-            F.scaler_sum, G.scaler_sum, P.scaler_sum});
+        tb[g.tips].push_back(triple_desc(F, G, P));
       } else {  // a deep pass: one launch each, ahead of the level's other work
         const int D = 6 - g.kind;
         add(out, kLaunchDeep, lv, g.tips, D, out->deeps.size(), 1);

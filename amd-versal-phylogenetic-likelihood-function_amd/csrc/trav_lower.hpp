@@ -5,6 +5,7 @@
 // (tests/trav_lower_main.cpp drives it on the CPU).
 #pragma once
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/plfx.h"
@@ -89,6 +90,47 @@ struct TravArrays {
   uint8_t *const *scalers;  // may be NULL
   int64_t *scaler_sums;     // may be NULL
 };
+
+// A node whose x1 / x2 name the uint8 codes of a coded child (t1 / t2).
+struct OpNode {
+  plfx_node nd;
+  bool t1, t2;
+};
+
+// Op j of a traversal as a node, children as the op names them; mat_bytes: of
+// one matrix (ncat * S * S values).
+inline OpNode op_node(const TravArrays &t, size_t mat_bytes, int j) {
+  const plfx_trav_op &o = t.ops[j];
+  const char *pmats = static_cast<const char *>(t.pmats);
+  const bool t1 = t.tips && t.tips[o.child1], t2 = t.tips && t.tips[o.child2];
+  return OpNode{{t1 ? (const void *)t.tips[o.child1] : t.clv[o.child1],
+                 t2 ? (const void *)t.tips[o.child2] : t.clv[o.child2], t.clv[o.parent],
+                 pmats + (size_t)(2 * o.pmat) * mat_bytes, pmats + (size_t)(2 * o.pmat + 1) * mat_bytes,
+                 t.scalers ? t.scalers[j] : nullptr, t.scaler_sums ? t.scaler_sums + j : nullptr},
+                t1, t2};
+}
+
+// Coded child first: dense/tip runs as tip/dense, (x1, left) swapped with
+// (x2, right).  Only u1[k] * u2[k] crosses the sides, so the bits are the same.
+inline OpNode tip_first(OpNode o) {
+  if (!o.t1 && o.t2) {
+    std::swap(o.nd.x1, o.nd.x2);
+    std::swap(o.nd.left, o.nd.right);
+    std::swap(o.t1, o.t2);
+  }
+  return o;
+}
+
+inline NodeDescH node_desc(const plfx_node &d) {
+  return NodeDescH{d.x1, d.x2, d.x3, d.left, d.right, d.scaler, d.scaler_sum};
+}
+
+// The level pair of leaf ops F, G and their parent op P, F the writer of P's child 1.
+inline TripleDescH triple_desc(const plfx_node &F, const plfx_node &G, const plfx_node &P) {
+  return TripleDescH{F.x1, F.x2, G.x1, G.x2, F.x3, G.x3, P.x3, (const double *)F.left, (const double *)F.right,
+                     (const double *)G.left, (const double *)G.right, (const double *)P.left, (const double *)P.right,
+                     F.scaler, G.scaler, P.scaler, F.scaler_sum, G.scaler_sum, P.scaler_sum};
+}
 
 // true when lower_traversal will use call.tt: protein with a tip/tip op
 bool traversal_uses_tables(const TravArrays &t, int states);

@@ -66,7 +66,8 @@ STREAM_PER_THREAD = 2  # hipStreamPerThread
 SCHED_KEYS = ("deep6", "deep5", "deep4", "septets", "triples", "unfused", "launches")
 PMAT_STATE, PMAT_EIGEN = 0, 1
 EXACT, FMA = 0, 1
-VALU = 2  # with FMA: protein f64 on the VALU, P matrices tiled in LDS (not the matrix cores)
+VALU = 2  # with FMA: protein f64 on the VALU (not the matrix cores): P and EV as wave-uniform scalar
+          # operands, LDS holds only the staged child tile
 PROT_CODES = 24  # protein tip codes: rows of the tip-vector table (plfx.h section 8)
 CTX_LAZY_TABLES = 1  # PLFX_CTX_LAZY_TABLES
 
@@ -298,7 +299,7 @@ class Context:
                 raise PlfxError(ERR_INVALID, "wgt shorter than n")
         inc = C.c_int(0)
         fn = self._L.plfx_plf_f32 if dt == np.float32 else self._L.plfx_plf_f64
-        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        p = _nptr
         self._check(fn(self.h, p(x1_start), p(x2_start), p(x3_start), p(EV), n, p(left), p(right),
                        p(w), C.byref(inc)))
         return inc.value
@@ -315,19 +316,13 @@ class Context:
         dt = x1.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        for t in (x1, x2, x3, EV, left, right):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise PlfxError(ERR_INVALID, "tensors must be contiguous device tensors of one dtype")
-        if n is None:
-            n = x1.numel() // 16
-        n = int(n)
-        if min(x1.numel(), x2.numel(), x3.numel()) < 16 * n:
-            raise PlfxError(ERR_INVALID, "CLV tensors shorter than 16*n")
-        if EV.numel() < 16 or left.numel() < 64 or right.numel() < 64:
-            raise PlfxError(ERR_INVALID, "EV needs 16, left/right 64 values")
+        n = x1.numel() // 16 if n is None else int(n)
+        for k, t, m in (("x1", x1, 16 * n), ("x2", x2, 16 * n), ("x3", x3, 16 * n), ("EV", EV, 16),
+                        ("left", left, 64), ("right", right, 64)):
+            _tensor(t, k, dt, m)
         _check_aux(n, wgt, scaler, scaler_sum)
         fn = self._L.plfx_plf_dev_f32 if dt == torch.float32 else self._L.plfx_plf_dev_f64
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _ptr
         self._check(fn(self.h, p(x1), p(x2), p(x3), p(EV), n, p(left), p(right), p(wgt),
                        p(scaler), p(scaler_sum), self._sh(stream)))
 
@@ -345,7 +340,7 @@ class Context:
                      stream=torch.cuda.current_stream(x1.device).cuda_stream)  # validates
         n = x1.numel() // 16 if n is None else int(n)
         fn = self._L.plfx_plf_dev_f32 if x1.dtype == torch.float32 else self._L.plfx_plf_dev_f64
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _ptr
         args = (self.h, p(x1), p(x2), p(x3), p(EV), C.c_int64(n), p(left), p(right), p(wgt),
                 p(scaler), p(scaler_sum))
         check = self._check
@@ -374,7 +369,7 @@ class Context:
             raise PlfxError(ERR_INVALID, "instance buffers too small for alignment_sites")
         if out_scaler is not None and (out_scaler.dtype != torch.uint8 or out_scaler.numel() < n):
             raise PlfxError(ERR_INVALID, "out_scaler must be uint8 with >= alignment_sites bytes")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _ptr
         self._check(self._L.plfx_instance_run(self.h, p(in_left), p(in_right), p(out_clv),
                                               p(out_scaler), n, int(window_size), int(layout),
                                               F32 if dt == torch.float32 else F64,
@@ -398,7 +393,7 @@ class Context:
         for a in (in_left, in_right, out_clv, out_scaler):
             if a is not None and not a.flags.c_contiguous:
                 raise PlfxError(ERR_INVALID, "instance buffers must be C-contiguous")
-        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        p = _nptr
         self._check(self._L.plfx_instance_run_host(self.h, p(in_left), p(in_right), p(out_clv),
                                                    p(out_scaler), n, int(window_size), int(layout),
                                                    F32 if dt == np.float32 else F64))
@@ -408,26 +403,21 @@ class Context:
         """Any built state count (4 DNA, 20 protein), 4 Gamma categories, on
         torch device tensors: x[site][cat][state], P [cat][k][l], EV [k][l].
         fma: PLFX_FMA; valu (with fma, protein f64): the same fused chains on
-        the VALU with LDS-tiled matrices instead of the matrix cores
-        (PLFX_VALU; bit-identical)."""
+        the VALU instead of the matrix cores, P and EV as wave-uniform scalar
+        operands, LDS holding only the staged child tile (PLFX_VALU;
+        bit-identical)."""
         import torch
 
-        V = 4 * states
+        V, S2 = 4 * states, states * states
         dt = x1.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        if n is None:
-            n = x1.numel() // V
-        n = int(n)
-        for t in (x1, x2, x3, EV, left, right):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise PlfxError(ERR_INVALID, "tensors must be contiguous device tensors of one dtype")
-        if min(x1.numel(), x2.numel(), x3.numel()) < V * n:
-            raise PlfxError(ERR_INVALID, "CLV tensors shorter than 4*states*n")
-        if EV.numel() < states * states or min(left.numel(), right.numel()) < 4 * states * states:
-            raise PlfxError(ERR_INVALID, "EV needs S*S, left/right 4*S*S values")
+        n = x1.numel() // V if n is None else int(n)
+        for k, t, m in (("x1", x1, V * n), ("x2", x2, V * n), ("x3", x3, V * n), ("EV", EV, S2),
+                        ("left", left, 4 * S2), ("right", right, 4 * S2)):
+            _tensor(t, k, dt, m)
         _check_aux(n, wgt, scaler, scaler_sum)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _ptr
         self._check(self._L.plfx_plf_dev_gen(self.h, F32 if dt == torch.float32 else F64, int(states),
                                              (FMA if fma else EXACT) | (VALU if valu else 0),
                                              p(x1), p(x2), p(x3), p(EV), n,
@@ -444,28 +434,20 @@ class Context:
         dt = EV.dtype
         V, M = 4 * states, 4 * states * states
         arr = (Node * len(nodes))()
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         for i, nd in enumerate(nodes):
             for k in ("x1", "x2", "x3"):
-                t = nd[k]
-                if t.dtype != dt or t.numel() < V * n or not t.is_contiguous() or not t.is_cuda:
-                    raise PlfxError(ERR_INVALID, f"node {i}: {k} must be a contiguous {dt} device "
-                                                 f"tensor >= {V}*n")
+                _tensor(nd[k], f"node {i}: {k}", dt, V * n)
             for k in ("left", "right"):
-                if nd[k].dtype != dt or nd[k].numel() < M or not nd[k].is_cuda or not nd[k].is_contiguous():
-                    raise PlfxError(ERR_INVALID, f"node {i}: {k} needs {M} contiguous device values")
+                _tensor(nd[k], f"node {i}: {k}", dt, M)
             try:
                 _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
             except PlfxError as e:
                 raise PlfxError(ERR_INVALID, f"node {i}: {e}") from None
-            arr[i] = Node(ptr(nd["x1"]), ptr(nd["x2"]), ptr(nd["x3"]), ptr(nd["left"]),
-                          ptr(nd["right"]), ptr(nd.get("scaler")), ptr(nd.get("scaler_sum")))
+            arr[i] = _node(nd)
         _check_aux(n, wgt, None, None)
-        if not EV.is_cuda or not EV.is_contiguous() or EV.numel() < states * states:
-            raise PlfxError(ERR_INVALID, f"EV must be a contiguous device tensor of {states * states} values")
+        _tensor(EV, "EV", dt, states * states)
         self._check(self._L.plfx_plf_batch_dev(self.h, F32 if dt == torch.float32 else F64, states, arr,
-                                               len(nodes), C.c_void_p(EV.data_ptr()), int(n),
-                                               C.c_void_p(ptr(wgt)), self._sh(stream)))
+                                               len(nodes), _ptr(EV), int(n), _ptr(wgt), self._sh(stream)))
 
     def bind_plf_batch_dev(self, nodes, EV, n, wgt=None, states=4):
         """Validate once (as plf_batch_dev) and return a launcher
@@ -479,13 +461,9 @@ class Context:
             return lambda stream=None: None
         self.plf_batch_dev(nodes, EV, n, wgt, stream=torch.cuda.current_stream(self.device).cuda_stream,
                            states=states)  # validates
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        arr = (Node * len(nodes))(*[Node(ptr(nd["x1"]), ptr(nd["x2"]), ptr(nd["x3"]), ptr(nd["left"]),
-                                         ptr(nd["right"]), ptr(nd.get("scaler")),
-                                         ptr(nd.get("scaler_sum"))) for nd in nodes])
+        arr = (Node * len(nodes))(*[_node(nd) for nd in nodes])
         fn, h, check = self._L.plfx_plf_batch_dev, self.h, self._check
-        args = (F32 if EV.dtype == torch.float32 else F64, states, arr, len(nodes),
-                C.c_void_p(EV.data_ptr()), int(n), C.c_void_p(ptr(wgt)))
+        args = (F32 if EV.dtype == torch.float32 else F64, states, arr, len(nodes), _ptr(EV), int(n), _ptr(wgt))
 
         ctx = self
 
@@ -509,57 +487,50 @@ class Context:
         PLFX_FMA for protein nodes."""
         import torch
 
-        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
-        nops = ops.shape[0]
         dt = EV.dtype
-        nslots = len(clv)
+        S2 = states * states
+        top, nops, slots, tp, nslots, npmats, sc = self._traverse_args(
+            ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, 4 * states, 4 * S2, S2)
+        self._check(self._L.plfx_traverse_tips(
+            self.h, F32 if dt == torch.float32 else F64, states, FMA if fma else EXACT, top, nops,
+            slots, tp, nslots, _ptr(pmats), npmats, _ptr(EV), int(n), _ptr(wgt), sc, _ptr(scaler_sums),
+            self._tipvec(tipvec, dt, states), self._sh(stream)))
+
+    @staticmethod
+    def _traverse_args(ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, V, M, ev):
+        """What traverse() and traverse_psr() share: the checks of the call's
+        tensors -- V values per CLV site, M per matrix, ev in EV, all of EV's
+        dtype -- and the ctypes arrays.  Returns (ops, nops, slots, tips,
+        nslots, npmats, scalers)."""
+        import torch
+
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
+        nops, nslots, dt = ops.shape[0], len(clv), EV.dtype
         if tips is not None and len(tips) != nslots:
             raise PlfxError(ERR_INVALID, "tips must have one entry per slot")
-        V, M = 4 * states, 4 * states * states
         for s_, t in enumerate(clv):
-            tip = None if tips is None else tips[s_]
-            if tip is not None:
-                if tip.dtype != torch.uint8 or tip.numel() < n or not tip.is_contiguous() or not tip.is_cuda:
-                    raise PlfxError(ERR_INVALID, f"tip slot {s_}: contiguous uint8 >= n required")
-                continue
-            if t is None or t.dtype != dt or t.numel() < V * n or not t.is_contiguous() or not t.is_cuda:
-                raise PlfxError(ERR_INVALID, f"every CLV slot must be a contiguous device tensor, "
-                                             f"same dtype, >= {V}*n")
-        if pmats.dtype != dt or pmats.numel() % (2 * M):
+            if tips is not None and tips[s_] is not None:
+                _tensor(tips[s_], f"tip slot {s_}", torch.uint8, n)
+            else:
+                _tensor(t, f"CLV slot {s_}", dt, V * n)
+        _tensor(pmats, "pmats", dt, 0)
+        if pmats.numel() % (2 * M):
             raise PlfxError(ERR_INVALID, f"pmats must hold whole (left, right) pairs of {M} values")
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or scaler_sums.numel() < nops
-                                        or not scaler_sums.is_cuda):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be an int64 device tensor with >= nops entries")
+        _tensor(scaler_sums, "scaler_sums", torch.int64, nops, contiguous=False, optional=True)
         if scalers is not None:
             if len(scalers) > nops:
                 raise PlfxError(ERR_INVALID, "more scaler tensors than ops")
             scalers = list(scalers) + [None] * (nops - len(scalers))
             for j, t in enumerate(scalers):
-                if t is not None and (t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous()
-                                      or t.numel() < n):
-                    raise PlfxError(ERR_INVALID, f"scaler of op {j} must be a contiguous uint8 "
-                                                 f"device tensor of >= n elements")
+                _tensor(t, f"scaler of op {j}", torch.uint8, n, optional=True)
         _check_aux(n, wgt, None, None)
-        for t in (pmats, EV):
-            if not t.is_cuda or not t.is_contiguous():
-                raise PlfxError(ERR_INVALID, "pmats and EV must be contiguous device tensors")
-        if EV.numel() < states * states:
-            raise PlfxError(ERR_INVALID, f"EV needs {states * states} values")
-        top = (TravOp * nops)(*[TravOp(*map(int, r)) for r in ops])
-        slots = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in clv])
-        tp = None
-        if tips is not None:
-            tp = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in tips])
-        sc = None
-        if scalers is not None:
-            sc = (C.c_void_p * nops)(*[None if t is None else t.data_ptr() for t in scalers])
-        self._check(self._L.plfx_traverse_tips(
-            self.h, F32 if dt == torch.float32 else F64, states, FMA if fma else EXACT, top, nops,
-            slots, tp, nslots, C.c_void_p(pmats.data_ptr()), pmats.numel() // (2 * M),
-            C.c_void_p(EV.data_ptr()), int(n),
-            C.c_void_p(None if wgt is None else wgt.data_ptr()), sc,
-            C.c_void_p(None if scaler_sums is None else scaler_sums.data_ptr()),
-            self._tipvec(tipvec, dt, states), self._sh(stream)))
+        _tensor(EV, "EV", dt, ev)
+        # at least one element: with no ops the library follows neither array
+        top = (TravOp * max(1, nops))(*[TravOp(*map(int, r)) for r in ops])
+        slots = (C.c_void_p * nslots)(*map(_ptr, clv))
+        tp = None if tips is None else (C.c_void_p * nslots)(*map(_ptr, tips))
+        sc = None if scalers is None else (C.c_void_p * max(1, nops))(*map(_ptr, scalers))
+        return top, nops, slots, tp, nslots, pmats.numel() // (2 * M), sc
 
     @staticmethod
     def _tipvec(tipvec, dt, states=4):
@@ -581,21 +552,15 @@ class Context:
         import torch
 
         dt = EV.dtype
-        V = 4 * states
+        S2 = states * states
         for k, t in (("x3", x3), ("x1", x1), ("x2", x2)):
-            if t is not None and (t.dtype != dt or t.numel() < V * n or not t.is_contiguous()
-                                  or not t.is_cuda):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= {V}*n")
+            _tensor(t, k, dt, 4 * states * n, optional=True)
         for k, t in (("tip1", tip1), ("tip2", tip2)):
-            if t is not None and (t.dtype != torch.uint8 or t.numel() < n or not t.is_contiguous()
-                                  or not t.is_cuda):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous uint8 device tensor >= n")
-        for k, t in (("EV", EV), ("left", left), ("right", right)):
-            if t.dtype != dt or not t.is_cuda or t.numel() < (states * states if k == "EV"
-                                                               else 4 * states * states):
-                raise PlfxError(ERR_INVALID, f"{k} must be a {dt} device tensor of the model's size")
+            _tensor(t, k, torch.uint8, n, optional=True)
+        for k, t, m in (("EV", EV, S2), ("left", left, 4 * S2), ("right", right, 4 * S2)):
+            _tensor(t, k, dt, m, contiguous=False)
         _check_aux(n, wgt, scaler, scaler_sum)
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
+        p = _ptr
         self._check(self._L.plfx_plf_tips_dev_gen(
             self.h, F32 if dt == torch.float32 else F64, states, FMA if fma else EXACT, p(tip1),
             p(x1), p(tip2), p(x2), p(x3), p(EV), int(n), p(left), p(right), p(wgt), p(scaler),
@@ -615,85 +580,81 @@ class Context:
         import torch
 
         S = states
-        for k, t in (("eigen", eigen), ("rates", rates), ("blen", blen)):
-            if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor")
-        if eigen.numel() < S + 2 * S * S:
-            raise PlfxError(ERR_INVALID, "eigen too small")
+        _tensor(eigen, "eigen", torch.float64, S + 2 * S * S)
+        _tensor(rates, "rates", torch.float64, 0)
+        _tensor(blen, "blen", torch.float64, 0)
         ncat, nb = rates.numel(), blen.numel()
-        if (out.dtype not in (torch.float32, torch.float64) or out.numel() < nb * ncat * S * S
-                or not out.is_cuda or not out.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "out must be a contiguous device tensor of nbranch*ncat*S*S "
-                                         "float values")
+        _tensor(out, "out", (torch.float32, torch.float64), nb * ncat * S * S)
         self._check(self._L.plfx_pmatrix(
-            self.h, F32 if out.dtype == torch.float32 else F64, S, convention,
-            C.c_void_p(eigen.data_ptr()), C.c_void_p(rates.data_ptr()), ncat,
-            C.c_void_p(blen.data_ptr()), nb, C.c_void_p(out.data_ptr()), self._sh(stream)))
+            self.h, F32 if out.dtype == torch.float32 else F64, S, convention, _ptr(eigen), _ptr(rates), ncat,
+            _ptr(blen), nb, _ptr(out), self._sh(stream)))
 
     # -- (7) root log-likelihood --------------------------------------------
     def root_lnl(self, x, n, out, catw=None, freq=None, wgt=None, scaler_sums=None,
                  site_lnl=None, states=4, stream=None):
         """Root lnL into `out` (float64 device tensor, 1 element); see plfx.h (7)."""
+        self._root_lnl(False, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream)
+
+    def _root_lnl(self, psr, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream):
+        """root_lnl (4 * states values per site) and root_lnl_psr (states)."""
         import torch
 
-        if out.dtype != torch.float64 or out.numel() < 1 or not out.is_cuda:
-            raise PlfxError(ERR_INVALID, "out must be a float64 device tensor")
-        if (x.dtype not in (torch.float32, torch.float64) or x.numel() < 4 * states * n
-                or not x.is_cuda or not x.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "x must be a contiguous float device tensor of >= 4*S*n values")
-        for t, k in ((catw, 4), (freq, states), (site_lnl, n)):
-            if t is not None and (t.dtype != torch.float64 or t.numel() < k or not t.is_cuda
-                                  or not t.is_contiguous()):
-                raise PlfxError(ERR_INVALID, "catw/freq/site_lnl must be contiguous float64 device "
-                                             "tensors (4 / S / n values)")
+        _tensor(out, "out", torch.float64, 1, contiguous=False)
+        _tensor(x, "x", (torch.float32, torch.float64), (1 if psr else 4) * states * n)
+        for k, t, m in (("catw", catw, 4), ("freq", freq, states), ("site_lnl", site_lnl, n)):
+            _tensor(t, k, torch.float64, m, optional=True)
         _check_aux(n, wgt, None, None)
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
-                                        or not scaler_sums.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        nsums = 0 if scaler_sums is None else scaler_sums.numel()
-        self._check(self._L.plfx_root_lnl(self.h, F32 if x.dtype == torch.float32 else F64, states,
-                                          p(x), int(n), p(catw), p(freq), p(wgt), p(scaler_sums),
-                                          nsums, p(out), p(site_lnl), self._sh(stream)))
+        _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
+        p = _ptr
+        dt = F32 if x.dtype == torch.float32 else F64
+        tail = (p(freq), p(wgt), p(scaler_sums), 0 if scaler_sums is None else scaler_sums.numel(), p(out),
+                p(site_lnl), self._sh(stream))
+        if psr:
+            self._check(self._L.plfx_root_lnl_psr(self.h, dt, p(x), int(n), *tail))
+        else:
+            self._check(self._L.plfx_root_lnl(self.h, dt, states, p(x), int(n), p(catw), *tail))
 
     # -- (10) one branch between two fixed CLVs -----------------------------
     def edge_sumtable(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
         """sumtab = x1 * x2 elementwise (plfx.h (10)); side 1 is the dense CLV
         x1 or the uint8 codes tip1 with the eigen-convention table tipvec
         (16 x 4 DNA, PROT_CODES x 20 protein).  CLVs in the eigen convention."""
+        self._edge_sumtable(False, states, x2, sumtab, n, x1, tip1, tipvec, stream)
+
+    def _edge_sumtable(self, psr, states, x2, sumtab, n, x1, tip1, tipvec, stream):
+        """edge_sumtable (4 * states values per site) and edge_sumtable_psr (states)."""
         import torch
 
         dt = sumtab.dtype
-        V = 4 * states
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
         for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
-            if t is not None and (t.dtype != dt or t.numel() < V * n or not t.is_contiguous()
-                                  or not t.is_cuda):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= {V}*n")
-        if tip1 is not None and (tip1.dtype != torch.uint8 or tip1.numel() < n or not tip1.is_contiguous()
-                                 or not tip1.is_cuda):
-            raise PlfxError(ERR_INVALID, "tip1 must be a contiguous uint8 device tensor >= n")
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        self._check(self._L.plfx_edge_sumtable(self.h, F32 if dt == torch.float32 else F64, int(states),
-                                               p(tip1), p(x1), p(x2), int(n),
-                                               self._tipvec(tipvec, dt, states), p(sumtab),
-                                               self._sh(stream)))
+            _tensor(t, k, dt, (1 if psr else 4) * states * n, optional=True)
+        _tensor(tip1, "tip1", torch.uint8, n, optional=True)
+        p = _ptr
+        tail = (p(tip1), p(x1), p(x2), int(n), self._tipvec(tipvec, dt, states), p(sumtab), self._sh(stream))
+        if psr:
+            self._check(self._L.plfx_edge_sumtable_psr(self.h, F32 if dt == torch.float32 else F64, *tail))
+        else:
+            self._check(self._L.plfx_edge_sumtable(self.h, F32 if dt == torch.float32 else F64, int(states), *tail))
 
-    def _edge_args(self, sumtab, n, eigen, rates, catw, wgt, states):
+    def _edge_args(self, sumtab, n, eigen, rates, catw, wgt, states, rate_cat=None, psr=False):
+        """The arguments the Gamma edge calls share (4 * states values per
+        site, catw) and, with psr, the per-site-rate ones (states, rate_cat)."""
         import torch
 
-        if (sumtab.dtype not in (torch.float32, torch.float64) or sumtab.numel() < 4 * states * n
-                or not sumtab.is_cuda or not sumtab.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "sumtab must be a contiguous float device tensor of >= 4*S*n values")
-        for k, t, m in (("eigen", eigen, states), ("rates", rates, 1), ("catw", catw, rates.numel())):
-            if t is not None and (t.dtype != torch.float64 or t.numel() < m or not t.is_cuda
-                                  or not t.is_contiguous()):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor")
+        _tensor(sumtab, "sumtab", (torch.float32, torch.float64), (1 if psr else 4) * states * n)
+        ncat = rates.numel()
+        _tensor(eigen, "eigen", torch.float64, states, optional=True)
+        _tensor(rates, "rates", torch.float64, 1)
+        if psr:
+            self._psr_cats(rate_cat, n)
+        else:
+            _tensor(catw, "catw", torch.float64, ncat, optional=True)
         _check_aux(n, wgt, None, None)
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        return (self.h, F32 if sumtab.dtype == torch.float32 else F64, int(states), p(sumtab), int(n),
-                p(eigen), p(rates), rates.numel(), p(catw), p(wgt))
+        p = _ptr
+        head = (self.h, F32 if sumtab.dtype == torch.float32 else F64) + (() if psr else (int(states),))
+        return head + (p(sumtab), int(n), p(eigen), p(rates), ncat, p(rate_cat if psr else catw), p(wgt))
 
     def edge_derivatives(self, sumtab, n, eigen, rates, t, out, catw=None, wgt=None, scaler_sums=None,
                          site_lnl=None, states=4, stream=None):
@@ -701,22 +662,21 @@ class Context:
         the branch whose sum table is `sumtab`, at the branch length in the
         device double `t`; see plfx.h (10).  eigen, rates: the device arrays
         pmatrix() takes."""
+        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
+        self._edge_derivatives(self._L.plfx_edge_derivatives, args, n, t, out, scaler_sums, site_lnl, stream)
+
+    def _edge_derivatives(self, fn, args, n, t, out, scaler_sums, site_lnl, stream):
+        """edge_derivatives and edge_derivatives_psr after their _edge_args."""
         import torch
 
-        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
         for k, x, m in (("t", t, 1), ("out", out, 3), ("site_lnl", site_lnl, n)):
-            if x is not None and (x.dtype != torch.float64 or x.numel() < m or not x.is_cuda
-                                  or not x.is_contiguous()):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor of >= {m}")
+            _tensor(x, k, torch.float64, m, optional=True)
         if t is None or out is None:
             raise PlfxError(ERR_INVALID, "t and out are required")
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
-                                        or not scaler_sums.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
-        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
+        _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
+        p = _ptr
         nsums = 0 if scaler_sums is None else scaler_sums.numel()
-        self._check(self._L.plfx_edge_derivatives(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl),
-                                                  self._sh(stream)))
+        self._check(fn(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl), self._sh(stream)))
 
     def optimize_branch(self, sumtab, n, eigen, rates, t0, tmin=1e-8, tmax=10.0, max_evals=64,
                         catw=None, wgt=None, states=4, stream=None):
@@ -749,11 +709,10 @@ class Context:
             args = self._edge_args(st, n, eigen, rates, catw, wgt, states)
         for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
                               ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
-            if x is not None and (x.dtype != dt or x.numel() < cnt or not x.is_cuda or not x.is_contiguous()):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor of >= {cnt}")
+            _tensor(x, k, dt, cnt, optional=True)
         if t0 is None or t_opt is None:
             raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
-        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
+        p = _ptr
         tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
         self._check(self._L.plfx_edge_optimize_dev(*args[:3], tabs, m, *args[4:], p(t0), float(tmin), float(tmax),
                                                    int(max_evals), p(t_opt), p(out3), p(evals), self._sh(stream)))
@@ -768,9 +727,7 @@ class Context:
     def _psr_cats(rate_cat, n):
         import torch
 
-        if (rate_cat is None or rate_cat.dtype != torch.uint8 or rate_cat.numel() < n or not rate_cat.is_cuda
-                or not rate_cat.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "rate_cat must be a contiguous uint8 device tensor of >= n elements")
+        _tensor(rate_cat, "rate_cat", torch.uint8, n)
 
     def plf_psr(self, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, states=4, stream=None):
         """Per-site-rate node updates (plfx.h section 11).  nodes: one dict or
@@ -788,33 +745,23 @@ class Context:
         dt = EV.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        if not EV.is_cuda or EV.numel() < 16:
-            raise PlfxError(ERR_INVALID, "EV must be a device tensor of 16 values")
+        _tensor(EV, "EV", dt, 16, contiguous=False)
         self._psr_cats(rate_cat, n)
         _check_aux(n, wgt, None, None)
         arr = (PsrNode * max(1, len(nodes)))()
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         for i, nd in enumerate(nodes):
             for k in ("x1", "x2", "x3"):
-                t = nd.get(k)
-                if t is not None and (t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda):
-                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= 4*n")
+                _tensor(nd.get(k), k, dt, 4 * n, optional=True)
             for k in ("tip1", "tip2"):
-                t = nd.get(k)
-                if t is not None and (t.dtype != torch.uint8 or t.numel() < n or not t.is_contiguous()
-                                      or not t.is_cuda):
-                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous uint8 device tensor >= n")
+                _tensor(nd.get(k), k, torch.uint8, n, optional=True)
             for k in ("left", "right"):
-                t = nd.get(k)
-                if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()
-                                      or t.numel() < 16 * max(ncat, 0)):
-                    raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor of ncat*16 values")
+                _tensor(nd.get(k), k, dt, 16 * max(ncat, 0), optional=True)
             _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
-            arr[i] = PsrNode(*(p(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
-                                                       "scaler", "scaler_sum")))
+            arr[i] = PsrNode(*(_ptr(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
+                                                          "scaler", "scaler_sum")))
         self._check(self._L.plfx_plf_psr_dev(
-            self.h, F32 if dt == torch.float32 else F64, arr, len(nodes), C.c_void_p(EV.data_ptr()), n,
-            C.c_void_p(rate_cat.data_ptr()), ncat, C.c_void_p(p(wgt)), self._tipvec(tipvec, dt), self._sh(stream)))
+            self.h, F32 if dt == torch.float32 else F64, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
+            _ptr(wgt), self._tipvec(tipvec, dt), self._sh(stream)))
 
     def traverse_psr(self, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None, scaler_sums=None,
                      stream=None, tips=None, tipvec=None, states=4):
@@ -829,143 +776,42 @@ class Context:
         import torch
 
         self._psr_states(states)
-        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
-        nops = ops.shape[0]
         n, ncat = int(n), int(ncat)
         dt = EV.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        nslots = len(clv)
-        if tips is not None and len(tips) != nslots:
-            raise PlfxError(ERR_INVALID, "tips must have one entry per slot")
-        for s_, t in enumerate(clv):
-            tip = None if tips is None else tips[s_]
-            if tip is not None:
-                if tip.dtype != torch.uint8 or tip.numel() < n or not tip.is_contiguous() or not tip.is_cuda:
-                    raise PlfxError(ERR_INVALID, f"tip slot {s_}: contiguous uint8 >= n required")
-                continue
-            if t is None or t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda:
-                raise PlfxError(ERR_INVALID, "every CLV slot must be a contiguous device tensor, same dtype, >= 4*n")
-        M = 16 * max(ncat, 1)
-        if pmats.dtype != dt or pmats.numel() % (2 * M):
-            raise PlfxError(ERR_INVALID, f"pmats must hold whole (left, right) pairs of {M} values")
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or scaler_sums.numel() < nops
-                                        or not scaler_sums.is_cuda):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be an int64 device tensor with >= nops entries")
-        if scalers is not None:
-            if len(scalers) > nops:
-                raise PlfxError(ERR_INVALID, "more scaler tensors than ops")
-            scalers = list(scalers) + [None] * (nops - len(scalers))
-            for j, t in enumerate(scalers):
-                if t is not None and (t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous()
-                                      or t.numel() < n):
-                    raise PlfxError(ERR_INVALID, f"scaler of op {j} must be a contiguous uint8 "
-                                                 f"device tensor of >= n elements")
+        top, nops, slots, tp, nslots, npmats, sc = self._traverse_args(
+            ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, 4, 16 * max(ncat, 1), 16)
         self._psr_cats(rate_cat, n)
-        _check_aux(n, wgt, None, None)
-        for t in (pmats, EV):
-            if not t.is_cuda or not t.is_contiguous():
-                raise PlfxError(ERR_INVALID, "pmats and EV must be contiguous device tensors")
-        if EV.numel() < 16:
-            raise PlfxError(ERR_INVALID, "EV needs 16 values")
-        top = (TravOp * max(1, nops))(*[TravOp(*map(int, r)) for r in ops])
-        slots = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in clv])
-        tp = None
-        if tips is not None:
-            tp = (C.c_void_p * nslots)(*[None if t is None else t.data_ptr() for t in tips])
-        sc = None
-        if scalers is not None:
-            sc = (C.c_void_p * max(1, nops))(*[None if t is None else t.data_ptr() for t in scalers])
         self._check(self._L.plfx_traverse_psr(
-            self.h, F32 if dt == torch.float32 else F64, top, nops, slots, tp, nslots,
-            C.c_void_p(pmats.data_ptr()), pmats.numel() // (2 * M), C.c_void_p(EV.data_ptr()), n,
-            C.c_void_p(rate_cat.data_ptr()), ncat, C.c_void_p(None if wgt is None else wgt.data_ptr()), sc,
-            C.c_void_p(None if scaler_sums is None else scaler_sums.data_ptr()), self._tipvec(tipvec, dt),
+            self.h, F32 if dt == torch.float32 else F64, top, nops, slots, tp, nslots, _ptr(pmats), npmats,
+            _ptr(EV), n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt),
             self._sh(stream)))
 
     def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
                      stream=None):
         """Root lnL of a per-site-rate CLV into `out` (float64 device tensor,
         1 element); plfx.h section 11."""
-        import torch
-
         self._psr_states(states)
-        if out.dtype != torch.float64 or out.numel() < 1 or not out.is_cuda:
-            raise PlfxError(ERR_INVALID, "out must be a float64 device tensor")
-        if (x.dtype not in (torch.float32, torch.float64) or x.numel() < 4 * n or not x.is_cuda
-                or not x.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "x must be a contiguous float device tensor of >= 4*n values")
-        for t, k in ((freq, 4), (site_lnl, n)):
-            if t is not None and (t.dtype != torch.float64 or t.numel() < k or not t.is_cuda
-                                  or not t.is_contiguous()):
-                raise PlfxError(ERR_INVALID, "freq/site_lnl must be contiguous float64 device tensors (4 / n values)")
-        _check_aux(n, wgt, None, None)
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
-                                        or not scaler_sums.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        nsums = 0 if scaler_sums is None else scaler_sums.numel()
-        self._check(self._L.plfx_root_lnl_psr(self.h, F32 if x.dtype == torch.float32 else F64, p(x), int(n),
-                                              p(freq), p(wgt), p(scaler_sums), nsums, p(out), p(site_lnl),
-                                              self._sh(stream)))
+        self._root_lnl(True, states, x, n, out, None, freq, wgt, scaler_sums, site_lnl, stream)
 
     def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
         """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the
         dense CLV x1 or the uint8 codes tip1 with the eigen-convention table."""
-        import torch
-
         self._psr_states(states)
-        dt = sumtab.dtype
-        if dt not in (torch.float32, torch.float64):
-            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
-            if t is not None and (t.dtype != dt or t.numel() < 4 * n or not t.is_contiguous() or not t.is_cuda):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous {dt} device tensor >= 4*n")
-        if tip1 is not None and (tip1.dtype != torch.uint8 or tip1.numel() < n or not tip1.is_contiguous()
-                                 or not tip1.is_cuda):
-            raise PlfxError(ERR_INVALID, "tip1 must be a contiguous uint8 device tensor >= n")
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        self._check(self._L.plfx_edge_sumtable_psr(self.h, F32 if dt == torch.float32 else F64, p(tip1), p(x1),
-                                                   p(x2), int(n), self._tipvec(tipvec, dt), p(sumtab),
-                                                   self._sh(stream)))
+        self._edge_sumtable(True, states, x2, sumtab, n, x1, tip1, tipvec, stream)
 
     def _edge_args_psr(self, sumtab, n, eigen, rates, rate_cat, wgt, states):
-        import torch
-
         self._psr_states(states)
-        if (sumtab.dtype not in (torch.float32, torch.float64) or sumtab.numel() < 4 * n
-                or not sumtab.is_cuda or not sumtab.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "sumtab must be a contiguous float device tensor of >= 4*n values")
-        for k, t, m in (("eigen", eigen, 4), ("rates", rates, 1)):
-            if t.dtype != torch.float64 or t.numel() < m or not t.is_cuda or not t.is_contiguous():
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor")
-        self._psr_cats(rate_cat, n)
-        _check_aux(n, wgt, None, None)
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
-        return (self.h, F32 if sumtab.dtype == torch.float32 else F64, p(sumtab), int(n), p(eigen), p(rates),
-                rates.numel(), p(rate_cat), p(wgt))
+        return self._edge_args(sumtab, n, eigen, rates, None, wgt, states, rate_cat, psr=True)
 
     def edge_derivatives_psr(self, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None, scaler_sums=None,
                              site_lnl=None, states=4, stream=None):
         """out (float64 device tensor, 3 elements) = lnL, d lnL/dt, d2 lnL/dt2 of
         the per-site-rate branch whose sum table is `sumtab`, at the device
         double `t`; rates holds the ncat category rates (plfx.h section 11)."""
-        import torch
-
         args = self._edge_args_psr(sumtab, n, eigen, rates, rate_cat, wgt, states)
-        for k, x, m in (("t", t, 1), ("out", out, 3), ("site_lnl", site_lnl, n)):
-            if x is not None and (x.dtype != torch.float64 or x.numel() < m or not x.is_cuda
-                                  or not x.is_contiguous()):
-                raise PlfxError(ERR_INVALID, f"{k} must be a contiguous float64 device tensor of >= {m}")
-        if t is None or out is None:
-            raise PlfxError(ERR_INVALID, "t and out are required")
-        if scaler_sums is not None and (scaler_sums.dtype != torch.int64 or not scaler_sums.is_cuda
-                                        or not scaler_sums.is_contiguous()):
-            raise PlfxError(ERR_INVALID, "scaler_sums must be a contiguous int64 device tensor")
-        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())  # noqa: E731
-        nsums = 0 if scaler_sums is None else scaler_sums.numel()
-        self._check(self._L.plfx_edge_derivatives_psr(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl),
-                                                      self._sh(stream)))
+        self._edge_derivatives(self._L.plfx_edge_derivatives_psr, args, n, t, out, scaler_sums, site_lnl, stream)
 
     def optimize_branch_psr(self, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0, max_evals=64,
                             wgt=None, states=4, stream=None):
@@ -986,7 +832,7 @@ class Context:
         if scaler.dtype != torch.uint8 or out_sum.dtype != torch.int64:
             raise PlfxError(ERR_INVALID, "scaler uint8, out_sum int64")
         _check_aux(n, wgt, scaler, out_sum)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _ptr
         self._check(self._L.plfx_scaler_sum(self.h, p(scaler), p(wgt), int(n), p(out_sum),
                                             self._sh(stream)))
 
@@ -1003,20 +849,45 @@ def _stream_handle(stream, device=None):
     return C.c_void_p(stream.cuda_stream)
 
 
+def _ptr(t):
+    """The address of a tensor's data as a c_void_p (None: NULL)."""
+    return C.c_void_p(None if t is None else t.data_ptr())
+
+
+def _nptr(a):
+    """The same of a numpy array."""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _node(nd):
+    """plfx_node of a node dict (absent scaler / scaler_sum: NULL)."""
+    return Node(*(_ptr(nd.get(k)) for k in ("x1", "x2", "x3", "left", "right", "scaler", "scaler_sum")))
+
+
+def _tensor(t, name, dtype, count, contiguous=True, optional=False):
+    """Refuse (PlfxError, ERR_INVALID) a tensor argument the library would
+    misread -- the C ABI sees a bare pointer: t must be a device tensor of
+    `dtype` (one dtype, or a tuple of the allowed ones) with at least `count`
+    elements, and contiguous where the call site demands it.  optional: None
+    passes (a NULL the library takes or refuses itself)."""
+    if t is None and optional:
+        return
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if (t is None or t.dtype not in dtypes or t.numel() < count or not t.is_cuda
+            or (contiguous and not t.is_contiguous())):
+        kinds = " / ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise PlfxError(ERR_INVALID, f"{name} must be a {'contiguous ' if contiguous else ''}{kinds} device tensor "
+                                     f"of >= {count} elements")
+
+
 def _check_aux(n, wgt, scaler, scaler_sum):
     """Shapes/dtypes/devices of the optional per-site weight, scaler bytes and
     scaler-sum outputs (the C ABI cannot see tensor sizes)."""
     import torch
 
-    if wgt is not None and (wgt.dtype != torch.int32 or wgt.numel() < n or not wgt.is_cuda
-                            or not wgt.is_contiguous()):
-        raise PlfxError(ERR_INVALID, "wgt must be a contiguous int32 device tensor of >= n elements")
-    if scaler is not None and (scaler.dtype != torch.uint8 or scaler.numel() < n or not scaler.is_cuda
-                               or not scaler.is_contiguous()):
-        raise PlfxError(ERR_INVALID, "scaler must be a contiguous uint8 device tensor of >= n elements")
-    if scaler_sum is not None and (scaler_sum.dtype != torch.int64 or scaler_sum.numel() < 1
-                                   or not scaler_sum.is_cuda):
-        raise PlfxError(ERR_INVALID, "scaler_sum must be an int64 device tensor")
+    _tensor(wgt, "wgt", torch.int32, n, optional=True)
+    _tensor(scaler, "scaler", torch.uint8, n, optional=True)
+    _tensor(scaler_sum, "scaler_sum", torch.int64, 1, contiguous=False, optional=True)
 
 
 def shard(total, parts, k):
@@ -1038,7 +909,7 @@ def gen_hostmem(n, dtype=np.float64, seed=20250117, wgt=True):
     out = dict(EV=np.empty(16, dt), left=np.empty(64, dt), right=np.empty(64, dt),
                x1=np.empty(16 * n, dt), x2=np.empty(16 * n, dt),
                wgt=np.empty(n, np.int32) if wgt else None)
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    p = _nptr
     rc = load().plfx_gen_hostmem(F32 if dt == np.float32 else F64, int(seed), int(n), p(out["EV"]),
                                  p(out["left"]), p(out["right"]), p(out["x1"]), p(out["x2"]),
                                  p(out["wgt"]))
@@ -1063,7 +934,7 @@ def swemu_instance_run(in_left, in_right, out_clv, out_scaler, alignment_sites, 
     if in_left.size < tb.instance_elements_left() or in_right.size < tb.instance_elements_right() \
             or out_clv.size < 16 * n or (out_scaler is not None and out_scaler.size < n):
         raise PlfxError(ERR_INVALID, "buffers smaller than the padded instance")
-    p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    p = _nptr
     rc = load().plfx_swemu_instance_run(p(in_left), p(in_right), p(out_clv), p(out_scaler), n,
                                         int(window_size), int(layout), int(aie_type),
                                         F32 if dt == np.float32 else F64)

@@ -1,6 +1,6 @@
 // psr_trav_lower_main.cpp -- the planning and lowering of a plfx_traverse_psr
 // call (csrc/trav_plan.cpp with states 4 and fuse <= 1, then
-// csrc/psr_trav_lower.cpp: checks, descriptors, per level the fused level
+// csrc/psr_lower.cpp: checks, descriptors, per level the fused level
 // pairs and the unfused ops) as a stand-alone program for
 // tests/test_psr_trav_lower.py (built with ASan + UBSan).  Every pointer is a
 // made-up address that is never followed:
@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "../amd-versal-phylogenetic-likelihood-function_amd/csrc/psr_trav_lower.hpp"
+#include "../amd-versal-phylogenetic-likelihood-function_amd/csrc/psr_lower.hpp"
 
 namespace {
 
@@ -42,7 +42,7 @@ unsigned long long hex(const void *p) { return (unsigned long long)reinterpret_c
 
 int main() {
   char word[32];
-  plfx::PsrTravList list;  // one list for every case, as a context keeps one
+  plfx::PsrLaunchList list;  // one list for every case, as a context keeps one
   while (scanf("%31s", word) == 1) {
     if (strcmp(word, "case")) return 2;
     int dtype, ncat, fuse, nslots, npmats, nops, nover;
@@ -100,8 +100,8 @@ int main() {
       printf("error %d %zu %zu %zu %s\n", rc, list.items.size(), list.triples.size(), list.nodes.size(), err.c_str());
     } else {
       printf("plan %d %d %d\n", plan.counts[plfx::kTravTriple], plan.counts[5], plan.nlev);
-      for (const plfx::PsrTravItem &it : list.items) {
-        const bool tr = it.kind == plfx::kPsrTravTriples;
+      for (const plfx::PsrLaunch &it : list.items) {
+        const bool tr = it.kind == plfx::kPsrTriples;
         printf("item %c %d %d %d\n", tr ? 't' : 'n', it.level, it.tips, it.count);
         for (int i = it.first; i < it.first + it.count; i++) {
           if (tr) {

@@ -1,5 +1,5 @@
 """The planning and lowering of a plfx_traverse_psr call on the CPU
-(csrc/trav_plan.cpp with fuse <= 1, then csrc/psr_trav_lower.cpp: checks,
+(csrc/trav_plan.cpp with fuse <= 1, then csrc/psr_lower.cpp: checks,
 descriptors, per level the fused level pairs in launches of at most 10 and the
 unfused ops by kind of children in launches of at most 32), as the stand-alone
 program tests/psr_trav_lower_main.cpp under ASan + UBSan.  The list is what
@@ -35,7 +35,7 @@ def lower(tmp_path_factory):
     exe = tmp_path_factory.mktemp("psr_trav_lower") / "psr_trav_lower_main"
     subprocess.run(["g++", "-std=c++17", *SAN, "-I", str(ROOT / "include"),
                     str(ROOT / "tests" / "psr_trav_lower_main.cpp"), str(CSRC / "trav_plan.cpp"),
-                    str(CSRC / "psr_trav_lower.cpp"), "-o", str(exe)],
+                    str(CSRC / "psr_lower.cpp"), "-o", str(exe)],
                    check=True, capture_output=True, text=True, timeout=300)
 
     def run(cases):
