@@ -19,6 +19,14 @@ struct NodeDescH {
 };
 constexpr int kMaxBatch = 32;
 
+// Batched PSR sum tables (plf_psr.hpp PsrEdgeDesc; <= kMaxBatch per launch,
+// all with the same kind of side 1): out = x1 * x2, x1 a dense CLV or the
+// uint8 codes of a coded side.
+struct PsrEdgeDescH {
+  const void *x1, *x2;
+  void *out;
+};
+
 // Tip/tip protein nodes from their 576-combination tables (plf_prot.hpp
 // prot_tiptip_gather_kernel): x3 / scaler / sum of each node gathered by code pair.
 struct ProtGatherDescH {

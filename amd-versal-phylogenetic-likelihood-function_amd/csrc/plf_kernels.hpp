@@ -132,6 +132,19 @@ hipError_t launch_edge_derivatives_psr(int dtype, const void *sumtab, int64_t n,
                                        const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
                                        double *partials, unsigned long long *ticket, double *out3,
                                        double *site_lnl, int max_blocks, hipStream_t s);
+// count <= kMaxBatch sum tables with one kind of side 1 in one launch (edge =
+// blockIdx.y), n >= 1; tip: every x1 names uint8 codes.
+hipError_t launch_edge_sumtable_psr_batch(int dtype, bool tip, const PsrEdgeDescH *edges, int count, int64_t n,
+                                          const void *tipvec, int max_blocks, hipStream_t s);
+// launch_edge_optimize for PSR sum tables (plf_psr.hpp edge_opt_psr_kernel):
+// state, partials and ws are the same regions.  A one-edge call has
+// launch_edge_derivatives_psr's grid.
+hipError_t launch_edge_optimize_psr(int dtype, const void *const *sumtabs, int count, int64_t n,
+                                    const double *lambda, const double *rates, int ncat,
+                                    const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                    double tmax, int max_evals, void *state, double *partials,
+                                    unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
+                                    int max_blocks, hipStream_t s);
 
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,

@@ -1,6 +1,7 @@
 // plf_psr.hip -- launchers of the per-site-rate kernels (plf_psr.hpp: the DNA
-// node, the root lnL, the sum table and the edge sums with one rate category
-// per site, plfx.h section 11).
+// node, the root lnL, the sum table -- one and batched --, the edge sums and
+// the branch-length loop on the device, with one rate category per site,
+// plfx.h section 11).
 //
 // Built into a library of its own, plfx/libplfx_psr.so, which libplfx.so
 // links, as plf_edge.hip is: libplfx.so's code objects and the pinned kernel
@@ -71,6 +72,19 @@ int64_t lnl_grid(K kernel, int &cache, int64_t n, int max_blocks) {
   return std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock * kStreamU, 1, max_blocks), kLnlMaxGrid);
 }
 
+// The grid of the edge sums, from edge_deriv_psr_kernel's occupancy: also the
+// one-edge grid of the device loop, whose sums then have that kernel's slots
+// and order.
+template <typename T>
+int64_t edge_deriv_psr_grid(int64_t n, int max_blocks) {
+  static int cache = 0;
+  return lnl_grid(&dev::edge_deriv_psr_kernel<T, kStreamU>, cache, n, max_blocks);
+}
+
+// the chunks of 4 x 16 B per thread a block of the sum-table kernels covers per trip, in sites
+template <typename T>
+constexpr int kSumtabSitesPerTrip = kBlock * 4 / (4 * (int)sizeof(T) / 16);
+
 }  // namespace
 
 hipError_t launch_plf_psr(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
@@ -121,9 +135,24 @@ hipError_t launch_edge_sumtable_psr(int dtype, bool tip, const void *x1, const v
         using T = real_t<k64()>;
         static int cache = 0;
         auto kernel = &dev::edge_sumtable_psr_kernel<T, kTip()>;
-        constexpr int kSitesPerTrip = kBlock * 4 / (4 * (int)sizeof(T) / 16);
-        const int64_t gx = grid_x((const void *)kernel, cache, n, kSitesPerTrip, 1, max_blocks);
+        const int64_t gx = grid_x((const void *)kernel, cache, n, kSumtabSitesPerTrip<T>, 1, max_blocks);
         return launch(kernel, dim3((unsigned)gx), kBlock, s, x1, (const T *)x2, n, (const T *)tipvec, (T *)sumtab);
+      },
+      bools{dtype == 1}, bools{tip});
+}
+
+hipError_t launch_edge_sumtable_psr_batch(int dtype, bool tip, const PsrEdgeDescH *edges, int count, int64_t n,
+                                          const void *tipvec, int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch || n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64, auto kTip) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::edge_sumtable_psr_batch_kernel<T, kTip()>;
+        const auto p = pack<dev::PsrEdgeBatch>(edges, count, [](const PsrEdgeDescH &) { return false; });
+        // an edge's share of the co-resident blocks, as a node's in launch_plf_psr_t
+        const int64_t gx = grid_x((const void *)kernel, cache, n, kSumtabSitesPerTrip<T>, count, max_blocks);
+        return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, p.b, n, (const T *)tipvec);
       },
       bools{dtype == 1}, bools{tip});
 }
@@ -137,11 +166,40 @@ hipError_t launch_edge_derivatives_psr(int dtype, const void *sumtab, int64_t n,
   return dispatch(
       [&](auto k64) {
         using T = real_t<k64()>;
-        static int cache = 0;
-        auto kernel = &dev::edge_deriv_psr_kernel<T, kStreamU>;
-        const int64_t gx = lnl_grid(kernel, cache, n, max_blocks);
-        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)sumtab, n, lambda, rates, ncat, rate_cat,
-                      wgt, t, scaler_sums, nsums, partials, ticket, out3, site_lnl);
+        const int64_t gx = edge_deriv_psr_grid<T>(n, max_blocks);
+        return launch(&dev::edge_deriv_psr_kernel<T, kStreamU>, dim3((unsigned)gx), kBlock, s, (const T *)sumtab, n,
+                      lambda, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums, partials, ticket, out3, site_lnl);
+      },
+      bools{dtype == 1});
+}
+
+// The device loop (plf_edge.hip launch_edge_opt_t for PSR tables): max_evals
+// launches of edge_opt_psr_kernel over the group's edges (blockIdx.y); the
+// first of them initialises the per-edge state.  The per-edge grid is the
+// one-edge grid unless the group's 3 * gx * count slots would not fit the
+// 3 * kLnlMaxGrid doubles of `partials`.
+hipError_t launch_edge_optimize_psr(int dtype, const void *const *sumtabs, int count, int64_t n,
+                                    const double *lambda, const double *rates, int ncat,
+                                    const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                    double tmax, int max_evals, void *state, double *partials,
+                                    unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
+                                    int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch || ncat < 1 || ncat > dev::kPsrMaxCats) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        dev::EdgeOptTabs a{};
+        for (int j = 0; j < count; j++) a.st[j] = sumtabs[j];
+        const int64_t gx =
+            std::max<int64_t>(1, std::min<int64_t>(edge_deriv_psr_grid<T>(n, max_blocks), kLnlMaxGrid / count));
+        for (int i = 0; i < max_evals; i++) {
+          hipError_t e = launch(&dev::edge_opt_psr_kernel<T, kStreamU>, dim3((unsigned)gx, (unsigned)count), kBlock,
+                                s, a, n, lambda, rates, ncat, rate_cat, wgt, t0, tmin, tmax, max_evals,
+                                (int)(i == 0), static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3,
+                                evals);
+          if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
       },
       bools{dtype == 1});
 }

@@ -401,9 +401,9 @@ root_lnl_psr_kernel(const T *__restrict__ x, int64_t n, const double *__restrict
 // per thread and trip (plf_edge.hpp edge_sumtable_kernel for one category).
 // kTip: side 1 is one code per site, x1[i][k] = tipvec[(code & 15)*4 + k].
 template <typename T, bool kTip>
-__global__ void __launch_bounds__(kBlock)
-edge_sumtable_psr_kernel(const void *__restrict__ x1, const T *__restrict__ x2, int64_t n,
-                         const T *__restrict__ tipvec, T *__restrict__ out) {
+__device__ __forceinline__ void edge_sumtable_psr_chunks(const void *__restrict__ x1, const T *__restrict__ x2,
+                                                         int64_t n, const T *__restrict__ tipvec,
+                                                         T *__restrict__ out) {
   using V = typename PsrRow<T>::V;
   constexpr int kVals = PsrRow<T>::kChunk;
   constexpr int kSite = 4 / kVals;  // chunks per site
@@ -438,6 +438,31 @@ edge_sumtable_psr_kernel(const void *__restrict__ x1, const T *__restrict__ x2, 
   }
 }
 
+template <typename T, bool kTip>
+__global__ void __launch_bounds__(kBlock)
+edge_sumtable_psr_kernel(const void *__restrict__ x1, const T *__restrict__ x2, int64_t n,
+                         const T *__restrict__ tipvec, T *__restrict__ out) {
+  edge_sumtable_psr_chunks<T, kTip>(x1, x2, n, tipvec, out);
+}
+
+// Up to kMaxBatch sum tables per launch (plfx_edge_sumtable_psr_batch), edge =
+// blockIdx.y, all with the same kind of side 1 (kTip: x1 names the codes):
+// each edge's table is the one-edge kernel's, chunk for chunk.
+struct PsrEdgeDesc {
+  const void *x1, *x2;
+  void *out;
+};
+struct PsrEdgeBatch {
+  PsrEdgeDesc d[kMaxBatch];
+};
+
+template <typename T, bool kTip>
+__global__ void __launch_bounds__(kBlock)
+edge_sumtable_psr_batch_kernel(const PsrEdgeBatch edges, int64_t n, const T *__restrict__ tipvec) {
+  const PsrEdgeDesc &d = edges.d[blockIdx.y];
+  edge_sumtable_psr_chunks<T, kTip>(d.x1, static_cast<const T *>(d.x2), n, tipvec, static_cast<T *>(d.out));
+}
+
 // The three edge sums of a PSR branch.  x_k = lambda_k * rates[c_i]; the
 // ncat x 4 factor triples {e, e x, e x x} are formed once per block from the
 // device t into LDS (rows of 12 doubles padded to 14: a stride of 7 slots,
@@ -445,7 +470,68 @@ edge_sumtable_psr_kernel(const void *__restrict__ x1, const T *__restrict__ x2, 
 // sum_k st[i][k] * {e, e1, e2} from +0.0, ascending k, in f64; the sums over
 // the sites as plf_edge.hpp's (edge_site, lnl_finish<3>).  n == 0: one block,
 // out = {correction, 0, 0}.
+//
+// edge_deriv_psr_sites: the block's factor table at branch length t and its
+// share of the sites into acc (blocks along x) -- edge_deriv_psr_kernel's
+// lines, statement for statement, as the body of edge_opt_psr_kernel.  The
+// derivative kernel keeps its own statement below: routed through this
+// function its register allocation changes (f64 110 -> 116 VGPRs, f32 98 ->
+// 104; LDS 3688 B and 4 waves per SIMD either way), as the node kernel's does
+// through psr_site.  The bits are the same: no contraction, one order.
+// partials: only a readable word here (wgt_at's dummy).
 constexpr int kPsrFactorStride = 14;
+template <typename T, int U>
+__device__ __forceinline__ void edge_deriv_psr_sites(const T *__restrict__ st, int64_t n,
+                                                     const double *__restrict__ lambda,
+                                                     const double *__restrict__ rates, int ncat,
+                                                     const uint8_t *__restrict__ rate_cat,
+                                                     const int32_t *__restrict__ wgt, const double t,
+                                                     const double *partials, double *__restrict__ site_lnl,
+                                                     double (&acc)[3]) {
+  __shared__ __attribute__((aligned(16))) double tab[kPsrMaxCats * kPsrFactorStride];
+  for (int i = threadIdx.x; i < ncat * 4; i += kBlock) {
+    const int c = i >> 2, k = i & 3;
+    double e0, e1, e2;
+    edge_factors(lambda[k], rates[c], t, e0, e1, e2);
+    tab[c * kPsrFactorStride + k] = e0;
+    tab[c * kPsrFactorStride + 4 + k] = e1;
+    tab[c * kPsrFactorStride + 8 + k] = e2;
+  }
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < n; base += stride) {
+    T v[U][4];
+    int cat[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      const int64_t ld = site < n ? site : nlast;
+      cat[u] = rate_cat[ld];
+      Num<T>::template load4<true>(st + ld * 4, v[u]);
+      w[u] = wgt_at(wgt, ld, partials);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t site = base + u * kBlock + threadIdx.x;
+      double f[12];
+      psr_lds_row<double, 12>(tab + psr_cat(cat[u], ncat) * kPsrFactorStride, f);
+      double L = 0.0, L1 = 0.0, L2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const double x = (double)v[u][k];
+        L += x * f[k];
+        L1 += x * f[4 + k];
+        L2 += x * f[8 + k];
+      }
+      if (site < n) {
+        const double l = edge_site(L, L1, L2, w[u], acc);
+        if (site_lnl) site_lnl[site] = l;
+      }
+    }
+  }
+}
+
 template <typename T, int U>
 __global__ void __launch_bounds__(kBlock)
 edge_deriv_psr_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
@@ -498,6 +584,34 @@ edge_deriv_psr_kernel(const T *__restrict__ st, int64_t n, const double *__restr
     }
   }
   lnl_finish<3>(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+// The branch-length loop on the device for PSR branches
+// (plfx_edge_optimize_psr_dev): plf_edge.hpp's edge_opt_kernel with the site
+// loop above.  One launch = one evaluation of every edge of the group that has
+// not stopped (blockIdx.y = edge, gridDim.x blocks per edge) and one step of
+// its bracket in the thread that holds the edge's totals; the state, ticket
+// and partial regions, the entry read and the step are that kernel's
+// (edge_opt_entry, edge_opt_step).  A stopped edge's blocks return before any
+// barrier, LDS write, partial or ticket.  Every block forms the factor table
+// from its edge's own t.
+template <typename T, int U>
+__global__ void __launch_bounds__(kBlock)
+edge_opt_psr_kernel(const EdgeOptTabs tabs, int64_t n, const double *__restrict__ lambda,
+                    const double *__restrict__ rates, int ncat, const uint8_t *__restrict__ rate_cat,
+                    const int32_t *__restrict__ wgt, const double *t0, double tmin, double tmax, int max_evals,
+                    int first, EdgeNewtonStep *state, double *partials, unsigned long long *ws, double *t_opt,
+                    double *out3, int32_t *evals) {
+  EdgeNewtonStep *sp = state + blockIdx.y;
+  bool done;
+  const double t = edge_opt_entry(sp, t0, tmin, tmax, first, done);
+  if (done) return;
+  const T *st = static_cast<const T *>(tabs.st[blockIdx.y]);
+  double *part = partials + (size_t)blockIdx.y * 3 * gridDim.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  edge_deriv_psr_sites<T, U>(st, n, lambda, rates, ncat, rate_cat, wgt, t, part, nullptr, acc);
+  if (lnl_finish<3, false>(acc, part, ws + (size_t)blockIdx.y * kWsWords, nullptr, nullptr, 0))
+    edge_opt_step(sp, acc, t, tmin, tmax, max_evals, first, t_opt, out3, evals);
 }
 
 }  // namespace dev

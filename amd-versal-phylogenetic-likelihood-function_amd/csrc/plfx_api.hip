@@ -19,6 +19,7 @@
 #include "../../include/plfx.h"
 #include "edge_newton.hpp"
 #include "plf_kernels.hpp"
+#include "psr_edge_lower.hpp"
 #include "psr_lower.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
@@ -60,6 +61,7 @@ struct plfx_ctx {
   int sched[PLFX_SCHED_COUNTS] = {};  // schedule of the last traverse
   plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
   plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev and plfx_traverse_psr
+  plfx::PsrEdgeLaunchList psr_edges_lowered;  // and for plfx_edge_sumtable_psr_batch
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -1255,6 +1257,53 @@ int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t
                             return plfx_edge_derivatives_psr(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt,
                                                              d_t, nullptr, 0, d_out, nullptr, stream);
                           });
+}
+
+
+int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges, int64_t n,
+                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                               const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                               double *t_opt, double *out3, int32_t *evals, void *stream) {
+  PLFX_BIND(ctx);
+  if (nedges < 1 || !sumtabs)
+    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: nedges=%d / null sumtabs", nedges);
+  for (int j = 0; j < nedges; j++) {
+    if (!sumtabs[j]) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: sum table %d is null", j);
+    if (int rc = check_psr_edge_args(ctx, dtype, sumtabs[j], n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
+  }
+  if (!t0 || !t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: null t0 / t_opt");
+  if (!(tmin > 0.0 && tmin <= tmax && std::isfinite(tmax)) || max_evals < 1 || max_evals > PLFX_EDGE_MAX_EVALS)
+    return fail(ctx, PLFX_ERR_INVALID,
+                "edge_optimize_psr_dev: needs 0 < tmin <= tmax < inf and 1 <= max_evals <= %d", PLFX_EDGE_MAX_EVALS);
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // groups of kMaxBatch edges, one after the other on the stream, in the
+  // regions and under the ordering rule of plfx_edge_optimize_dev
+  for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
+    const int c = std::min(nedges - g, plfx::kMaxBatch);
+    hipError_t e = plfx::launch_edge_optimize_psr(dtype, sumtabs + g, c, n, eigen, rates, ncat, rate_cat, wgt, t0 + g,
+                                                  tmin, tmax, max_evals, w->edge_state, w->lnl_partials, w->ws,
+                                                  t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
+                                                  evals ? evals + g : nullptr, ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_psr_dev launch");
+  }
+  return PLFX_OK;
+}
+
+int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges, int64_t n,
+                                 const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  std::string err;
+  plfx::PsrEdgeLaunchList &l = ctx->psr_edges_lowered;
+  if (plfx::lower_psr_edges(dtype, n, tipvec, edges, nedges, &l, &err) != PLFX_OK)
+    return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  hipStream_t s = pick(stream);
+  for (const plfx::PsrEdgeLaunch &it : l.items) {  // none when n == 0
+    hipError_t e = plfx::launch_edge_sumtable_psr_batch(dtype, it.tip != 0, &l.edges[it.first], it.count, n, tipvec,
+                                                        ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr_batch launch");
+  }
+  return PLFX_OK;
 }
 
 }  // extern "C"

@@ -56,6 +56,7 @@ EXPORTS = (
     "plfx_edge_sumtable", "plfx_edge_derivatives", "plfx_edge_optimize", "plfx_edge_optimize_dev",
     "plfx_plf_psr_dev", "plfx_root_lnl_psr", "plfx_edge_sumtable_psr", "plfx_edge_derivatives_psr",
     "plfx_edge_optimize_psr", "plfx_traverse_psr",
+    "plfx_edge_optimize_psr_dev", "plfx_edge_sumtable_psr_batch",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -90,6 +91,11 @@ class PsrNode(C.Structure):
     _fields_ = [("tip1", C.c_void_p), ("x1", C.c_void_p), ("tip2", C.c_void_p), ("x2", C.c_void_p),
                 ("x3", C.c_void_p), ("left", C.c_void_p), ("right", C.c_void_p), ("scaler", C.c_void_p),
                 ("scaler_sum", C.c_void_p)]
+
+
+class PsrEdge(C.Structure):
+    """plfx_psr_edge: one branch of a batched per-site-rate sum table (all device pointers)."""
+    _fields_ = [("tip1", C.c_void_p), ("x1", C.c_void_p), ("x2", C.c_void_p), ("sumtab", C.c_void_p)]
 
 
 class TravOp(C.Structure):
@@ -188,6 +194,9 @@ def load():
                                          C.POINTER(i32), vp]
     L.plfx_traverse_psr.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, vp,
                                     i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
+    L.plfx_edge_optimize_psr_dev.argtypes = [vp, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl, i32,
+                                             vp, vp, vp, vp]
+    L.plfx_edge_sumtable_psr_batch.argtypes = [vp, i32, C.POINTER(PsrEdge), i32, i64, vp, vp]
     _lib = L
     return L
 
@@ -822,6 +831,57 @@ class Context:
         self._check(self._L.plfx_edge_optimize_psr(*args, float(t0), float(tmin), float(tmax), int(max_evals),
                                                    C.byref(t), out, C.byref(ev), self._sh(stream)))
         return t.value, out[0], out[1], out[2], ev.value
+
+    def optimize_branches_psr(self, sumtabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=1e-8, tmax=10.0,
+                              max_evals=64, out3=None, evals=None, wgt=None, states=4, stream=None):
+        """optimize_branches for per-site-rate branches, with the loop on the
+        device (plfx_edge_optimize_psr_dev): asynchronous, capture-safe.
+        sumtabs: device tensors of 4*n values each; rate_cat, rates as
+        edge_derivatives_psr; t0, t_opt, out3, evals as optimize_branches."""
+        import torch
+
+        m = len(sumtabs)
+        if m < 1:
+            raise PlfxError(ERR_INVALID, "sumtabs must hold at least one sum table")
+        for st in sumtabs:
+            if st.dtype != sumtabs[0].dtype:
+                raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
+            args = self._edge_args_psr(st, n, eigen, rates, rate_cat, wgt, states)
+        for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
+                              ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
+            _tensor(x, k, dt, cnt, optional=True)
+        if t0 is None or t_opt is None:
+            raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
+        p = _ptr
+        tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
+        self._check(self._L.plfx_edge_optimize_psr_dev(*args[:2], tabs, m, *args[3:], p(t0), float(tmin),
+                                                       float(tmax), int(max_evals), p(t_opt), p(out3), p(evals),
+                                                       self._sh(stream)))
+
+    def edge_sumtables_psr(self, edges, n, tipvec=None, states=4, stream=None):
+        """The sum tables of many per-site-rate branches in one call
+        (plfx_edge_sumtable_psr_batch).  edges: a list of dicts with x2,
+        sumtab and exactly one of x1 / tip1, as edge_sumtable_psr's arguments;
+        every table of the call must be apart from every other table and
+        from every input, inputs may repeat."""
+        import torch
+
+        self._psr_states(states)
+        if isinstance(edges, dict):
+            edges = [edges]
+        n = int(n)
+        dt = edges[0]["sumtab"].dtype if edges and edges[0].get("sumtab") is not None else torch.float64
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        arr = (PsrEdge * max(1, len(edges)))()
+        for i, e in enumerate(edges):
+            for k in ("x1", "x2", "sumtab"):
+                _tensor(e.get(k), k, dt, 4 * n, optional=True)
+            _tensor(e.get("tip1"), "tip1", torch.uint8, n, optional=True)
+            arr[i] = PsrEdge(*(_ptr(e.get(k)) for k in ("tip1", "x1", "x2", "sumtab")))
+        self._check(self._L.plfx_edge_sumtable_psr_batch(
+            self.h, F32 if dt == torch.float32 else F64, arr, len(edges), n, self._tipvec(tipvec, dt),
+            self._sh(stream)))
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):

@@ -700,11 +700,70 @@ int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int6
 
 /* plfx_edge_optimize over plfx_edge_derivatives_psr: the same bracketed Newton
  * iteration, stop rules, argument rules and refusal of a capturing stream;
- * host-synchronous.  (There is no device-resident PSR loop.) */
+ * host-synchronous. */
 int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
                            const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
                            double t0, double tmin, double tmax, int max_evals, double *t_opt,
                            double *out3_host, int *evals, void *stream);
+
+/* plfx_edge_optimize_dev for PSR branches: the contract of section (10)'s
+ * device loop with the PSR arguments of plfx_edge_derivatives_psr.  sumtabs:
+ * HOST array of nedges device PSR sum tables (n * 4 values of dtype each,
+ * 16-byte aligned, none NULL; the pointers travel in the kernel arguments);
+ * n, eigen, rates, ncat, rate_cat and wgt are shared by all edges.  t0
+ * (device, read by the first launch, clamped into [tmin, tmax], a NaN starts
+ * at tmin), t_opt, out3 and evals (device; the last two may be NULL) as
+ * there.  Exactly max_evals launches per group of up to 32 edges, edge =
+ * blockIdx.y, groups one after the other on the stream; asynchronous,
+ * allocates nothing, legal on a capturing stream; the stream's workspace
+ * regions are the ones plfx_edge_optimize_dev uses.  Every edge walks the t
+ * sequence plfx_edge_optimize_psr walks from the same start, and a one-edge
+ * call has plfx_edge_derivatives_psr's grid, slots and summation order, so
+ * its t_opt, out3 and evals are plfx_edge_optimize_psr's bit for bit.  In a
+ * group of `count` edges each edge gets at most 4096 / count blocks, so with
+ * many edges of many sites the sums are formed in another (fixed) order.
+ * Deterministic.  n == 0 is accepted (rate_cat may then be NULL): every edge
+ * walks the host loop's sequence on the sums {0, 0, 0}.
+ * PLFX_ERR_INVALID, before the first launch: what plfx_edge_derivatives_psr
+ * refuses of dtype, ncat (outside 1..PLFX_PSR_MAX_CATS), n, eigen, rates,
+ * rate_cat and each table; nedges < 1; a NULL sumtabs, t0 or t_opt; anything
+ * but 0 < tmin <= tmax < infinity and 1 <= max_evals <= PLFX_EDGE_MAX_EVALS.
+ * There is no PLFX_ERR_UNSUPPORTED case. */
+int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges,
+                               int64_t n, const double *eigen, const double *rates, int ncat,
+                               const uint8_t *rate_cat, const int32_t *wgt, const double *t0,
+                               double tmin, double tmax, int max_evals, double *t_opt,
+                               double *out3, int32_t *evals, void *stream);
+
+/* One branch of plfx_edge_sumtable_psr_batch: exactly one of tip1 / x1 is
+ * non-NULL.  All device pointers. */
+typedef struct {
+  const uint8_t *tip1; /* exactly one of tip1 / x1 */
+  const void *x1;
+  const void *x2;
+  void *sumtab;
+} plfx_psr_edge;
+
+/* The sum tables of nedges >= 1 PSR branches sharing n and tipvec: edge j's
+ * table is exactly what plfx_edge_sumtable_psr writes for the same arguments
+ * (one multiply rounded in dtype, no other byte written).  `edges` is host
+ * memory and travels in the kernel arguments: the edges with a dense side 1
+ * first, then those with a coded one, each kind in the caller's order in
+ * launches of up to 32 edges (edge = blockIdx.y).  Asynchronous, allocates
+ * nothing, needs no workspace, capture-safe.  With plfx_edge_optimize_psr_dev
+ * a batch of branches goes from CLVs to optima in 1-2 + max_evals launches
+ * per 32 branches with no host wait.
+ * Every check runs before the first launch (PLFX_ERR_INVALID, nothing is
+ * launched): nedges < 1, a NULL edges, n < 0, a bad dtype; per edge the rules
+ * of plfx_edge_sumtable_psr (both or neither of tip1 / x1, a NULL x2 or
+ * sumtab, a dense side or a table not 16-byte aligned, a coded side with
+ * tipvec NULL, a table sharing a byte with its own x1 / tip1 or x2); across
+ * the call a table that shares a byte with another edge's table (the same
+ * table listed twice included) or with any edge's input.  Inputs may repeat
+ * freely: one CLV is an end of three branches.  n == 0 runs the call-level
+ * checks only and launches nothing. */
+int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges,
+                                 int64_t n, const void *tipvec, void *stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -25,8 +25,21 @@
 # under PLFX_FUSE=1 (fused level pairs).  A library without plfx_traverse_psr
 # gets row (i) alone: that run is the baseline of the other two.
 #
+# `--optimize` measures a branch-length optimisation instead, by the method of
+# tools/edge_bench.py --optimize: f64, ncat 25, two-taxon PSR alignments
+# simulated at distances between 0.05 and 1, every edge started at t0 = 0.1 on
+# [1e-8, 10]; the host loop (plfx_edge_optimize_psr: one call per edge, a host
+# wait per evaluation), the device loop (plfx_edge_optimize_psr_dev: one call
+# for all edges) issued eagerly and as a replayed graph, for 1 and 32 edges,
+# max_evals 64 and 16, at 10^4 and 2^20 sites, with the evaluations each path
+# made; then 32 plfx_edge_sumtable_psr calls against one
+# plfx_edge_sumtable_psr_batch call at both sizes.  Host-clock times around
+# work that ends in a synchronisation, the paths alternating within every
+# round, the median over the rounds after a warm-up round.
+#
 #   python tools/psr_bench.py [--calls 200] [--rounds 7] [--sites N] [--big]
 #   python tools/psr_bench.py --tree [--calls 200] [--rounds 7]
+#   python tools/psr_bench.py --optimize [--rounds 7]
 import argparse
 import statistics
 import sys
@@ -218,6 +231,105 @@ def tree_main(a):
         c.close()
 
 
+def alternate(paths, reps, rounds):
+    """{name: [us per call]} of host-clock times, the paths alternating within every round; round 0 warms up."""
+    import time
+
+    us = {k: [] for k in paths}
+    for rnd in range(rounds + 1):
+        for name, fn in paths.items():
+            torch.cuda.synchronize()
+            b = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            if rnd:
+                us[name].append((time.perf_counter() - b) * 1e6 / reps)
+    return us
+
+
+def optimize_main(a):
+    """--optimize: see the head of this file."""
+    ctx = plfx.Context(0, lazy_tables=True)
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()  # noqa: E731
+    rng = np.random.default_rng(4)
+    e = plfx.model_eigen(rng.random(6) + 0.5, rng.random(4) + 0.5)
+    lam, Vm, Vi = e[:4], e[4:20].reshape(4, 4), e[20:].reshape(4, 4)
+    rates_np = np.geomspace(0.05, 4.0, NCAT)
+    eig, rates = dev(e), dev(rates_np)
+    Vit = dev(Vi.T)  # row s: the eigen coordinates of state s
+    for n in (10 ** 4, 1 << 20):
+        gen = torch.Generator(device="cuda").manual_seed(n % 1000)
+        cat = torch.randint(0, NCAT, (n,), dtype=torch.uint8, device="cuda", generator=gen)
+        wgt = torch.ones(n, dtype=torch.int32, device="cuda")
+        ends, all_tables = [], []
+        for j in range(32):
+            tstar = float(np.geomspace(0.05, 1.0, 32)[j])
+            P = np.stack([np.clip((Vm * np.exp(lam * r * tstar)) @ Vi, 0, None) for r in rates_np])  # (ncat, 4, 4)
+            Pt = dev(P / P.sum(axis=2, keepdims=True))
+            sa = torch.randint(0, 4, (n,), device="cuda", generator=gen)
+            sb = torch.multinomial(Pt[cat.long(), sa], 1, generator=gen).squeeze(1)
+            ends.append((Vit[sa].contiguous().reshape(-1), Vit[sb].contiguous().reshape(-1)))
+            all_tables.append(ends[-1][0] * ends[-1][1])
+        for nedges in (1, 32):
+            tables = all_tables[:nedges] if nedges > 1 else all_tables[15:16]
+            t0 = torch.full((nedges,), 0.1, dtype=torch.float64, device="cuda")
+            t_opt = torch.zeros(nedges, dtype=torch.float64, device="cuda")
+            evals = torch.zeros(nedges, dtype=torch.int32, device="cuda")
+            for max_evals in (64, 16):
+                side = torch.cuda.Stream()
+                host_evals = []
+
+                def host():
+                    host_evals.clear()
+                    for st in tables:
+                        host_evals.append(ctx.optimize_branch_psr(st, n, eig, rates, cat, 0.1, 1e-8, 10.0, max_evals,
+                                                                  wgt=wgt, stream=side)[4])
+
+                def device():
+                    ctx.optimize_branches_psr(tables, n, eig, rates, cat, t0, t_opt, 1e-8, 10.0, max_evals, evals=evals,
+                                              wgt=wgt, stream=side)
+
+                device()  # the stream's workspace, outside the capture
+                side.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    device()
+                paths = {"host loop": host, "device loop, eager": device, "device loop, graph": g.replay}
+                us = alternate(paths, 100 if n <= 100000 else 5, a.rounds)
+                dev_evals = evals.cpu().numpy()
+                for name in paths:
+                    med = statistics.median(us[name])
+                    ev = host_evals if name == "host loop" else dev_evals.tolist()
+                    print(f"psr f64 ncat={NCAT} n={n} optimise edges={nedges:2d} max_evals={max_evals} {name:19s} "
+                          f"{med:10.1f} us (min {min(us[name]):.1f} max {max(us[name]):.1f}) {med / nedges:9.1f} us/edge "
+                          f"evals used mean {np.mean(ev):.1f} max {max(ev)}", flush=True)
+                del g
+                torch.cuda.synchronize()
+                ctx.release_stream(side)
+        # the sum tables of the 32 edges: one call each against one batch call
+        outs = [torch.empty(4 * n, dtype=torch.float64, device="cuda") for _ in range(32)]
+        edges = [dict(x1=x1, x2=x2, sumtab=o) for (x1, x2), o in zip(ends, outs)]
+        side = torch.cuda.Stream()
+
+        def singles():
+            for d in edges:
+                ctx.edge_sumtable_psr(d["x2"], d["sumtab"], n, x1=d["x1"], stream=side)
+
+        def batch():
+            ctx.edge_sumtables_psr(edges, n, stream=side)
+
+        paths = {"32 single calls": singles, "one batch call": batch}
+        us = alternate(paths, 100 if n <= 100000 else 5, a.rounds)
+        for name in paths:
+            med = statistics.median(us[name])
+            print(f"psr f64 n={n} sum tables edges=32 dense {name:19s} {med:10.1f} us (min {min(us[name]):.1f} "
+                  f"max {max(us[name]):.1f}) {med / 32:9.1f} us/edge", flush=True)
+        del ends, all_tables, outs, edges
+        torch.cuda.empty_cache()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
@@ -226,11 +338,16 @@ def main():
     ap.add_argument("--big", action="store_true", help="add the dense/dense PSR rows at 2^23 sites")
     ap.add_argument("--tree", action="store_true",
                     help="instead: one traversal of the balanced 64-taxon coded-tip tree, three routes, 2^14 and 2^20 sites")
+    ap.add_argument("--optimize", action="store_true",
+                    help="instead: a branch-length optimisation by the host loop and the device loop, and 32 sum tables "
+                         "one by one against one batch call, 10^4 and 2^20 sites")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("psr_bench needs a GPU")
     if a.tree:
         return tree_main(a)
+    if a.optimize:
+        return optimize_main(a)
     ctx = plfx.Context(0, lazy_tables=True)
     for dt, label in ((torch.float64, "f64"), (torch.float32, "f32")):
         n = a.sites
