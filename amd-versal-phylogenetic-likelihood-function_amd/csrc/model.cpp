@@ -7,6 +7,7 @@
 // substitution per unit time, and Yang (1994) discrete Gamma (mean or median
 // of each of K equal-probability categories).  Host-only code (no device
 // work); the P matrices themselves are built on the device (plf_pmat.hpp).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -187,6 +188,64 @@ int plfx_gamma_rates(double alpha, int ncat, int median, double *rates) {
     rates[i] = ncat * (cur - prev);
     prev = cur;
   }
+  return PLFX_OK;
+}
+
+// plfx.h section 12: the scan's best candidates binned into at most max_cats
+// categories.  Every argument is checked before anything is written.
+int plfx_psr_categorize(const double *cand_rates, int ncand, const int32_t *best_idx, const int32_t *wgt,
+                        int64_t n, int max_cats, uint8_t *rate_cat, double *cat_rates, int *ncat,
+                        double *scale) {
+  if (!cand_rates || !best_idx || !rate_cat || !cat_rates || !ncat || !scale || n < 1 || ncand < 1 ||
+      max_cats < 1 || max_cats > PLFX_PSR_MAX_CATS)
+    return PLFX_ERR_INVALID;
+  for (int k = 0; k < ncand; k++)
+    if (!std::isfinite(cand_rates[k]) || !(cand_rates[k] > 0.0)) return PLFX_ERR_INVALID;
+  std::vector<int64_t> W((size_t)ncand, 0);
+  std::vector<char> chosen((size_t)ncand, 0);
+  int64_t wsum = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const int k = best_idx[i];
+    const int64_t w = wgt ? wgt[i] : 1;
+    if (k < 0 || k >= ncand || w < 0) return PLFX_ERR_INVALID;
+    W[(size_t)k] += w;
+    chosen[(size_t)k] = 1;
+    wsum += w;
+  }
+  if (wsum == 0) return PLFX_ERR_INVALID;
+  std::vector<int> kept;
+  for (int k = 0; k < ncand; k++)
+    if (chosen[(size_t)k]) kept.push_back(k);
+  if ((int)kept.size() > max_cats) {  // the max_cats heaviest, ties to the lower k
+    std::stable_sort(kept.begin(), kept.end(), [&](int a, int b) { return W[(size_t)a] > W[(size_t)b]; });
+    kept.resize((size_t)max_cats);
+  }
+  // categories by ascending rate, ties by k
+  std::sort(kept.begin(), kept.end(), [&](int a, int b) {
+    return cand_rates[a] < cand_rates[b] || (cand_rates[a] == cand_rates[b] && a < b);
+  });
+  const int nc = (int)kept.size();
+  std::vector<int> cat_of((size_t)ncand, -1);
+  for (int c = 0; c < nc; c++) cat_of[(size_t)kept[(size_t)c]] = c;
+  for (int k = 0; k < ncand; k++) {  // a dropped candidate: the nearest kept rate, ties to the lower category
+    if (!chosen[(size_t)k] || cat_of[(size_t)k] >= 0) continue;
+    int best = 0;
+    for (int c = 1; c < nc; c++)
+      if (std::fabs(cand_rates[k] - cand_rates[kept[(size_t)c]]) < std::fabs(cand_rates[k] - cand_rates[kept[(size_t)best]]))
+        best = c;
+    cat_of[(size_t)k] = best;
+  }
+  double sw = 0.0, swr = 0.0;
+  for (int64_t i = 0; i < n; i++) {
+    const int c = cat_of[(size_t)best_idx[i]];
+    const double w = wgt ? (double)wgt[i] : 1.0;
+    rate_cat[i] = (uint8_t)c;
+    sw += w;
+    swr += w * cand_rates[kept[(size_t)c]];
+  }
+  *scale = sw / swr;
+  for (int c = 0; c < nc; c++) cat_rates[c] = cand_rates[kept[(size_t)c]] * *scale;
+  *ncat = nc;
   return PLFX_OK;
 }
 

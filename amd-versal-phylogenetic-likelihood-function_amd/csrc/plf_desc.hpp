@@ -27,6 +27,13 @@ struct PsrEdgeDescH {
   void *out;
 };
 
+// One tip of a tiling launch of the PSR rate scan (plf_psr.hpp PsrTileDesc; <=
+// kMaxBatch per launch): dst[g * n + i] = src[i] for every candidate g of a group.
+struct PsrTileDescH {
+  const uint8_t *src;
+  uint8_t *dst;
+};
+
 // Tip/tip protein nodes from their 576-combination tables (plf_prot.hpp
 // prot_tiptip_gather_kernel): x3 / scaler / sum of each node gathered by code pair.
 struct ProtGatherDescH {

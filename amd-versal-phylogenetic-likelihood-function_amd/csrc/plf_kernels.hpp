@@ -146,6 +146,24 @@ hipError_t launch_edge_optimize_psr(int dtype, const void *const *sumtabs, int c
                                     unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
                                     int max_blocks, hipStream_t s);
 
+// The per-site rate scan (plfx.h section 12; plf_psr.hpp psr_site_lnl_kernel,
+// psr_tile_kernel), n >= 1.  scalers: nsc rows `stride` bytes apart (may be
+// NULL with nsc == 0).  site_lnl: one segment, per-site lnL with the site's own
+// scaling correction, no workspace.  scan_pass: gc candidates from k0 over
+// gc * n virtual sites of x, the running best updated (`first`: started), the
+// weighted total into out through partials / ticket when out != NULL.  tile:
+// count <= kMaxBatch tips tiled `group` times and, when cat != NULL, the
+// group * n category bytes.
+hipError_t launch_psr_site_lnl(int dtype, const void *x, int64_t n, const double *freq, const uint8_t *scalers,
+                               int nsc, int64_t stride, double *site_lnl, int max_blocks, hipStream_t s);
+hipError_t launch_psr_scan_pass(int dtype, const void *x, int64_t n, int gc, const double *freq,
+                                const uint8_t *scalers, int nsc, int64_t stride, int k0, bool first,
+                                double *all_lnl, double *best_lnl, int32_t *best_idx, const int32_t *wgt,
+                                double *partials, unsigned long long *ticket, double *out, int max_blocks,
+                                hipStream_t s);
+hipError_t launch_psr_tile(const PsrTileDescH *tips, int count, int64_t n, int group, uint8_t *cat, int max_blocks,
+                           hipStream_t s);
+
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,
                              hipStream_t s);

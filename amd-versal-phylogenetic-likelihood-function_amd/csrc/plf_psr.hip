@@ -29,6 +29,7 @@ using bools = among<false, true>;
 template <typename T>
 constexpr int kNodeU = sizeof(T) == 8 ? 2 : 4;
 constexpr int kStreamU = 4;  // root lnL, edge sums: one 32-B / 16-B load per site
+constexpr int kScanU = 2;    // rate scan: candidates of a site per trip, their loads issued together
 
 // The node is an HBM stream: the share of the co-resident blocks its node
 // count leaves each node (grid_x), node = blockIdx.y.
@@ -202,6 +203,54 @@ hipError_t launch_edge_optimize_psr(int dtype, const void *const *sumtabs, int c
         return hipSuccess;
       },
       bools{dtype == 1});
+}
+
+// ---- plfx.h section 12 ----
+
+// One block per kBlock sites, capped at the co-resident blocks and at the
+// partial slots of lnl_finish.
+hipError_t launch_psr_site_lnl(int dtype, const void *x, int64_t n, const double *freq, const uint8_t *scalers,
+                               int nsc, int64_t stride, double *site_lnl, int max_blocks, hipStream_t s) {
+  if (n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::psr_site_lnl_kernel<T, false, 1>;
+        const int64_t gx = grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, 1, freq, scalers, nsc, stride, 0, 1,
+                      site_lnl, (double *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, (double *)nullptr,
+                      (unsigned long long *)nullptr, (double *)nullptr);
+      },
+      bools{dtype == 1});
+}
+
+hipError_t launch_psr_scan_pass(int dtype, const void *x, int64_t n, int gc, const double *freq,
+                                const uint8_t *scalers, int nsc, int64_t stride, int k0, bool first,
+                                double *all_lnl, double *best_lnl, int32_t *best_idx, const int32_t *wgt,
+                                double *partials, unsigned long long *ticket, double *out, int max_blocks,
+                                hipStream_t s) {
+  if (n < 1 || gc < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::psr_site_lnl_kernel<T, true, kScanU>;
+        const int64_t gx = std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks), kLnlMaxGrid);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, gc, freq, scalers, nsc, stride, k0,
+                      (int)first, all_lnl, best_lnl, best_idx, wgt, partials, ticket, out);
+      },
+      bools{dtype == 1});
+}
+
+hipError_t launch_psr_tile(const PsrTileDescH *tips, int count, int64_t n, int group, uint8_t *cat, int max_blocks,
+                           hipStream_t s) {
+  if (count < 0 || count > kMaxBatch || (count == 0 && !cat) || n < 1 || group < 1) return hipErrorInvalidValue;
+  static int cache = 0;
+  const auto p = pack<dev::PsrTileBatch>(tips, count, [](const PsrTileDescH &) { return false; });
+  const int rows = count + (cat ? 1 : 0);
+  const int64_t gx = grid_x((const void *)&dev::psr_tile_kernel, cache, (int64_t)group * n, kBlock, rows, max_blocks);
+  return launch(&dev::psr_tile_kernel, dim3((unsigned)gx, (unsigned)rows), kBlock, s, p.b, count, n, group, cat);
 }
 
 }  // namespace plfx

@@ -614,5 +614,110 @@ edge_opt_psr_kernel(const EdgeOptTabs tabs, int64_t n, const double *__restrict_
     edge_opt_step(sp, acc, t, tmin, tmax, max_evals, first, t_opt, out3, evals);
 }
 
+// ---- plfx.h section 12: the per-site rate scan ----
+//
+// Per-site lnL with the site's own scaling correction over a "virtual
+// alignment" of G segments of n sites (virtual site g * n + i = site i under
+// candidate k0 + g), and the running argmax over the candidates.  One lane
+// owns site i and walks g:
+//   L   = sum_s freq[s] * x[(g*n + i)*4 + s]    root_lnl_psr_kernel's statement
+//   cnt = sum_{j < nsc} (scalers[j*stride + g*n + i] != 0)
+//   lnl = log(L) + (double)cnt * log(2^-32)     one multiply, one add
+// A wave's 64 lanes read 64 consecutive bytes of a scaler row and 64
+// consecutive CLV rows: the kernel streams nsc + 4 * sizeof(T) bytes per
+// virtual site.  U candidates per trip, all their loads issued first (clamped
+// to the last candidate, results unused past G).
+// kBest: candidate k0 + g replaces (best_lnl, best_idx) iff lnl > best_lnl
+// (ties keep the lower index, a NaN never wins), from (-inf, 0) when `first`,
+// else from what the earlier passes left; out != NULL (the last pass): out =
+// sum_i wgt_i * best_lnl[i] through lnl_finish.  all_lnl may be NULL.
+template <typename T, bool kBest, int U>
+__global__ void __launch_bounds__(kBlock)
+psr_site_lnl_kernel(const T *__restrict__ x, int64_t n, int G, const double *__restrict__ freq,
+                    const uint8_t *__restrict__ scalers, int nsc, int64_t stride, int k0, int first,
+                    double *__restrict__ all_lnl, double *best_lnl, int32_t *best_idx,
+                    const int32_t *__restrict__ wgt, double *partials, unsigned long long *ticket, double *out) {
+  double fr[4];
+#pragma unroll
+  for (int s = 0; s < 4; s++) fr[s] = freq ? freq[s] : 0.25;
+  double acc = 0.0;
+  const int64_t step = (int64_t)gridDim.x * kBlock;
+  for (int64_t site = (int64_t)blockIdx.x * kBlock + threadIdx.x; site < n; site += step) {
+    double bl = -__builtin_inf();
+    int bi = 0;
+    if constexpr (kBest) {
+      if (!first) {
+        bl = best_lnl[site];
+        bi = best_idx[site];
+      }
+    }
+    for (int g0 = 0; g0 < G; g0 += U) {
+      T v[U][4];
+      int cnt[U];
+      int64_t vs[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int g = g0 + u < G ? g0 + u : G - 1;
+        vs[u] = (int64_t)g * n + site;
+        Num<T>::template load4<true>(x + vs[u] * 4, v[u]);
+        cnt[u] = 0;
+      }
+#pragma unroll 4
+      for (int j = 0; j < nsc; j++) {
+        const uint8_t *row = scalers + (int64_t)j * stride;
+#pragma unroll
+        for (int u = 0; u < U; u++) cnt[u] += row[vs[u]] != 0 ? 1 : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        double L = 0.0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) L += fr[s] * (double)v[u][s];
+        const double corr = (double)cnt[u] * kLogMinLik;
+        const double l = log(L) + corr;
+        if (g0 + u < G) {
+          if (all_lnl) all_lnl[(int64_t)(k0 + g0 + u) * n + site] = l;
+          if (kBest && l > bl) {
+            bl = l;
+            bi = k0 + g0 + u;
+          }
+        }
+      }
+    }
+    if constexpr (kBest) {
+      best_lnl[site] = bl;
+      best_idx[site] = bi;
+      if (out) acc += (double)wgt_at(wgt, site, partials) * bl;
+    }
+  }
+  if constexpr (kBest) {
+    if (out) lnl_finish(acc, partials, ticket, out, nullptr, 0);  // uniform: a kernel argument
+  }
+}
+
+// The scan's set-up: tip t of the launch (blockIdx.y < count) tiled G times,
+// dst[g*n + i] = src[i]; blockIdx.y == count (launched when cat != NULL): the
+// category bytes cat[g*n + i] = g.
+struct PsrTileDesc {
+  const uint8_t *src;
+  uint8_t *dst;
+};
+struct PsrTileBatch {
+  PsrTileDesc d[kMaxBatch];
+};
+
+__global__ void __launch_bounds__(kBlock)
+psr_tile_kernel(const PsrTileBatch tips, int count, int64_t n, int G, uint8_t *__restrict__ cat) {
+  const int64_t total = (int64_t)G * n;
+  const int64_t step = (int64_t)gridDim.x * kBlock;
+  const bool is_cat = (int)blockIdx.y >= count;
+  const PsrTileDesc &d = tips.d[is_cat ? 0 : blockIdx.y];
+  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < total; v += step) {
+    const int64_t g = v / n;
+    if (is_cat) cat[v] = (uint8_t)g;
+    else d.dst[v] = d.src[v - g * n];
+  }
+}
+
 }  // namespace dev
 }  // namespace plfx

@@ -21,6 +21,7 @@
 #include "plf_kernels.hpp"
 #include "psr_edge_lower.hpp"
 #include "psr_lower.hpp"
+#include "psr_scan_lower.hpp"
 #include "stream_ws.hpp"
 #include "testbench.hpp"
 #include "trav_lower.hpp"
@@ -62,6 +63,7 @@ struct plfx_ctx {
   plfx::LaunchList lowered;         // the launches of the call in progress (kept for its capacity)
   plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev and plfx_traverse_psr
   plfx::PsrEdgeLaunchList psr_edges_lowered;  // and for plfx_edge_sumtable_psr_batch
+  plfx::PsrScanPlan psr_scan;       // and for plfx_psr_rate_scan
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -1302,6 +1304,71 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
     hipError_t e = plfx::launch_edge_sumtable_psr_batch(dtype, it.tip != 0, &l.edges[it.first], it.count, n, tipvec,
                                                         ctx->max_blocks, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr_batch launch");
+  }
+  return PLFX_OK;
+}
+
+// ---- (12) the PSR rate scan ----
+
+int plfx_site_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const uint8_t *scalers, int nsc, int64_t stride, double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (n < 0 || !x || !aligned16(x) || !site_lnl || nsc < 0 || (nsc > 0 && !scalers) || stride < n)
+    return fail(ctx, PLFX_ERR_INVALID,
+                "site_lnl_psr: needs n >= 0, a 16-byte aligned x, site_lnl, nsc >= 0 rows (non-NULL when nsc > 0) and "
+                "stride >= n");
+  if (n == 0) return PLFX_OK;
+  hipError_t e = plfx::launch_psr_site_lnl(dtype, x, n, freq, scalers, nsc, stride, site_lnl, ctx->max_blocks,
+                                           pick(stream));
+  if (e != hipSuccess) return hip_fail(ctx, e, "site_lnl_psr launch");
+  return PLFX_OK;
+}
+
+int plfx_psr_rate_scan_workspace(int dtype, int nops, int ntips, int npmats, int64_t n, int group, size_t *bytes) {
+  plfx::PsrScanLayout lay;
+  if (!bytes || plfx::psr_scan_layout(dtype, nops, ntips, npmats, n, group, &lay) != PLFX_OK) return PLFX_ERR_INVALID;
+  *bytes = lay.end;
+  return PLFX_OK;
+}
+
+int plfx_psr_rate_scan(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, const uint8_t *const *tips,
+                       int nslots, const double *blen, int npmats, const double *eigen, const void *EV,
+                       const void *tipvec, const double *cand_rates, int ncand, int group, const double *freq,
+                       const int32_t *wgt, int64_t n, void *workspace, size_t workspace_bytes, int32_t *best_idx,
+                       double *best_lnl, double *all_lnl, double *out_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  // lower: every check, the workspace carved, the passes and each pass's launch list, before the first launch
+  plfx::PsrScanPlan &pl = ctx->psr_scan;
+  const plfx::PsrScanCall call{dtype,  ops,        nops,  tips,  nslots, blen,      npmats,          eigen,
+                               EV,     tipvec,     cand_rates,   ncand,  group,     n,               workspace,
+                               workspace_bytes,    best_idx,     best_lnl,          all_lnl,         out_lnl,
+                               ctx->psr_fuse};
+  std::string err;
+  if (int rc = plfx::lower_psr_scan(call, &pl, &err); rc != PLFX_OK) return fail(ctx, rc, "%s", err.c_str());
+  hipStream_t s = pick(stream);
+  if (n == 0) return zero_sums(ctx, s, out_lnl, 1);
+  PLFX_WS(ctx, s, w);
+  // set-up: the tip codes and the category bytes over the whole group
+  const int ntile = (int)pl.tiles.size();
+  for (int i = 0; i == 0 || i < ntile; i += plfx::kMaxBatch) {
+    hipError_t e = plfx::launch_psr_tile(ntile ? &pl.tiles[(size_t)i] : nullptr, std::min(plfx::kMaxBatch, ntile - i),
+                                         n, group, i == 0 ? pl.cat : nullptr, ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan tiling launch");
+  }
+  // passes, one after the other on the stream: each reuses the CLVs, scaler rows and matrices
+  for (size_t p = 0; p < pl.passes.size(); p++) {
+    const plfx::PsrScanPass &ps = pl.passes[p];
+    hipError_t e = plfx::launch_pmatrix(dtype, true, eigen, 4, cand_rates + ps.k0, ps.gc, blen, 2 * (int64_t)npmats,
+                                        pl.pmats, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan pmatrix launch");
+    const plfx::PsrCall pc{dtype, (int64_t)ps.gc * n, ps.gc, EV, pl.cat};
+    if (int rc = execute_psr(ctx, ps.tail ? pl.tail : pl.full, pc, nullptr, tipvec, s, w->ws); rc != PLFX_OK) return rc;
+    const bool last = p + 1 == pl.passes.size();
+    e = plfx::launch_psr_scan_pass(dtype, pl.root, n, ps.gc, freq, pl.scalers, nops, pl.sc_stride, ps.k0, p == 0,
+                                   all_lnl, best_lnl, best_idx, wgt, w->lnl_partials, w->lnl_ticket,
+                                   last ? out_lnl : nullptr, ctx->max_blocks, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan lnl launch");
   }
   return PLFX_OK;
 }

@@ -57,9 +57,11 @@ EXPORTS = (
     "plfx_plf_psr_dev", "plfx_root_lnl_psr", "plfx_edge_sumtable_psr", "plfx_edge_derivatives_psr",
     "plfx_edge_optimize_psr", "plfx_traverse_psr",
     "plfx_edge_optimize_psr_dev", "plfx_edge_sumtable_psr_batch",
+    "plfx_site_lnl_psr", "plfx_psr_rate_scan", "plfx_psr_rate_scan_workspace", "plfx_psr_categorize",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
+PSR_SCAN_MAX_RATES = 1024  # PLFX_PSR_SCAN_MAX_RATES
 MAX_STREAMS = 64   # PLFX_MAX_STREAMS
 WS_POOL = 8        # PLFX_WS_POOL
 STREAMS_MAX = 8    # PLFX_STREAMS_MAX
@@ -197,6 +199,11 @@ def load():
     L.plfx_edge_optimize_psr_dev.argtypes = [vp, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl, i32,
                                              vp, vp, vp, vp]
     L.plfx_edge_sumtable_psr_batch.argtypes = [vp, i32, C.POINTER(PsrEdge), i32, i64, vp, vp]
+    L.plfx_site_lnl_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, i64, vp, vp]
+    L.plfx_psr_rate_scan.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, i32,
+                                     i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.plfx_psr_rate_scan_workspace.argtypes = [i32, i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)]
+    L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
     _lib = L
     return L
 
@@ -883,6 +890,80 @@ class Context:
             self.h, F32 if dt == torch.float32 else F64, arr, len(edges), n, self._tipvec(tipvec, dt),
             self._sh(stream)))
 
+    # -- (12) the PSR rate scan ----------------------------------------------
+    def site_lnl_psr(self, x, n, site_lnl, freq=None, scalers=None, nsc=None, stride=None, states=4, stream=None):
+        """Per-site lnL of a per-site-rate CLV with the site's own scaling
+        correction (plfx.h section 12): site_lnl[i] = log(sum_s freq[s] x[i][s])
+        + (number of rows j < nsc with scalers[j*stride + i] != 0) * log(2^-32).
+        scalers: one uint8 device tensor holding the nsc rows (2-D: nsc and
+        stride default to its shape; 1-D: pass both), or None for nsc = 0."""
+        import torch
+
+        self._psr_states(states)
+        n = int(n)
+        _tensor(x, "x", (torch.float32, torch.float64), 4 * n)
+        _tensor(site_lnl, "site_lnl", torch.float64, n)
+        _tensor(freq, "freq", torch.float64, 4, optional=True)
+        if scalers is None:
+            nsc, stride = (0 if nsc is None else int(nsc)), (n if stride is None else int(stride))
+        else:
+            if scalers.dim() == 2 and nsc is None and stride is None:
+                nsc, stride = scalers.shape
+            if nsc is None or stride is None:
+                raise PlfxError(ERR_INVALID, "scalers must be 2-D (nsc x stride), or pass nsc and stride")
+            nsc, stride = int(nsc), int(stride)
+            _tensor(scalers, "scalers", torch.uint8, max(nsc - 1, 0) * max(stride, 0) + n if nsc > 0 else 0)
+        self._check(self._L.plfx_site_lnl_psr(
+            self.h, F32 if x.dtype == torch.float32 else F64, _ptr(x), n, _ptr(freq), _ptr(scalers), nsc, stride,
+            _ptr(site_lnl), self._sh(stream)))
+
+    def psr_rate_scan(self, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx, best_lnl,
+                      group=PSR_MAX_CATS, freq=None, wgt=None, all_lnl=None, out_lnl=None, states=4, stream=None):
+        """The per-site rate scan (plfx.h section 12, plfx_psr_rate_scan): for
+        every candidate rate the per-site lnL of the whole tree with all sites
+        at that rate, and per site the best candidate.  ops: (nops, 4) int
+        array of [parent, child1, child2, pmat]; tips: list (per slot) of uint8
+        code tensors or None -- every leaf must be coded; blen: float64 device
+        tensor of 2*npmats branch lengths; eigen as pmatrix(); EV, tipvec in
+        the eigen convention (their dtype is the CLVs'); cand_rates: float64
+        device tensor; workspace: a torch.uint8 device tensor of at least
+        psr_rate_scan_workspace(...) bytes, 256-byte aligned; best_idx
+        (int32[n]), best_lnl (float64[n]), all_lnl (float64[ncand*n], optional)
+        and out_lnl (float64[1], optional) are written.  group: candidates per
+        traversal (sizes the workspace; the outputs do not depend on it)."""
+        import torch
+
+        self._psr_states(states)
+        n, group = int(n), int(group)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
+        nops, nslots = ops.shape[0], len(tips)
+        for s_, t in enumerate(tips):
+            _tensor(t, f"tip slot {s_}", torch.uint8, n, optional=True)
+        _tensor(blen, "blen", torch.float64, 0)
+        if blen.numel() % 2:
+            raise PlfxError(ERR_INVALID, "blen must hold whole (left, right) pairs")
+        npmats, ncand = blen.numel() // 2, 0 if cand_rates is None else cand_rates.numel()
+        _tensor(eigen, "eigen", torch.float64, 4 + 2 * 16)
+        _tensor(EV, "EV", dt, 16)
+        _tensor(cand_rates, "cand_rates", torch.float64, 0)
+        _tensor(freq, "freq", torch.float64, 4, optional=True)
+        _check_aux(n, wgt, None, None)
+        _tensor(workspace, "workspace", torch.uint8, 0)
+        _tensor(best_idx, "best_idx", torch.int32, n)
+        _tensor(best_lnl, "best_lnl", torch.float64, n)
+        _tensor(all_lnl, "all_lnl", torch.float64, ncand * n, optional=True)
+        _tensor(out_lnl, "out_lnl", torch.float64, 1, optional=True)
+        top = (TravOp * max(1, nops))(*[TravOp(*map(int, r)) for r in ops])
+        tp = (C.c_void_p * max(1, nslots))(*map(_ptr, tips))
+        self._check(self._L.plfx_psr_rate_scan(
+            self.h, F32 if dt == torch.float32 else F64, top, nops, tp, nslots, _ptr(blen), npmats, _ptr(eigen),
+            _ptr(EV), self._tipvec(tipvec, dt), _ptr(cand_rates), ncand, group, _ptr(freq), _ptr(wgt), n,
+            _ptr(workspace), workspace.numel(), _ptr(best_idx), _ptr(best_lnl), _ptr(all_lnl), _ptr(out_lnl),
+            self._sh(stream)))
+
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):
         import torch
@@ -1035,6 +1116,39 @@ def gamma_rates(alpha, ncat=4, median=False):
     out, op = _dbl(np.zeros(ncat))
     _host_check(L.plfx_gamma_rates(float(alpha), int(ncat), 1 if median else 0, op), "gamma_rates")
     return out
+
+
+def psr_rate_scan_workspace(dtype, nops, ntips, npmats, n, group=PSR_MAX_CATS):
+    """Bytes of the workspace psr_rate_scan() needs (plfx.h section 12).  dtype:
+    F32 / F64, a numpy dtype or a torch dtype; ntips: the coded tips."""
+    if not isinstance(dtype, int):
+        name = str(dtype).replace("torch.", "")
+        if name not in ("float32", "float64"):
+            name = np.dtype(dtype).name
+        dtype = {"float32": F32, "float64": F64}.get(name, -1)
+    out = C.c_size_t(0)
+    _host_check(load().plfx_psr_rate_scan_workspace(int(dtype), int(nops), int(ntips), int(npmats), int(n),
+                                                    int(group), C.byref(out)), "psr_rate_scan_workspace")
+    return int(out.value)
+
+
+def psr_categorize(cand_rates, best_idx, wgt=None, max_cats=PSR_MAX_CATS):
+    """The scan's best candidates binned into at most max_cats categories
+    (plfx.h section 12, plfx_psr_categorize), on numpy arrays.  Returns
+    (rate_cat uint8[n], cat_rates float64[ncat], scale): cat_rates are the kept
+    candidates times scale, so that the weighted mean rate is 1."""
+    r, rp = _dbl(cand_rates)
+    idx = np.ascontiguousarray(best_idx, dtype=np.int32).reshape(-1)
+    w = None if wgt is None else np.ascontiguousarray(wgt, dtype=np.int32).reshape(-1)
+    if w is not None and w.size != idx.size:
+        raise PlfxError(ERR_INVALID, "wgt must have one entry per site")
+    max_cats = int(max_cats)
+    cat = np.zeros(idx.size, np.uint8)
+    rates, ratesp = _dbl(np.zeros(max(max_cats, 1)))
+    ncat, scale = C.c_int(0), C.c_double(0.0)
+    _host_check(load().plfx_psr_categorize(rp, r.size, _nptr(idx), _nptr(w), idx.size, max_cats, _nptr(cat), ratesp,
+                                           C.byref(ncat), C.byref(scale)), "psr_categorize")
+    return cat, rates[:ncat.value].copy(), float(scale.value)
 
 
 def model_ev(eigen, states, convention=PMAT_STATE):

@@ -765,6 +765,100 @@ typedef struct {
 int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges,
                                  int64_t n, const void *tipvec, void *stream);
 
+/* ---- (12) the PSR rate scan and rate categorisation (extension) -----------
+ * Section (11) takes rate_cat and the category rates as inputs; this section
+ * produces them, as RAxML / ExaML do for GTRCAT: every site gets the rate it
+ * likes best on the current tree out of a grid of candidates, and the chosen
+ * rates are binned into at most max_cats categories.
+ *
+ * Per-site lnL with the site's own scaling correction:
+ *   L_i    = sum_s freq[s] * x[i][s]                (plfx_root_lnl_psr's L_i)
+ *   cnt_i  = number of j < nsc with scalers[j*stride + i] != 0
+ *   site_lnl[i] = log(L_i) + cnt_i * log(2^-32)     (one multiply, one add)
+ * x: a PSR CLV (n * 4 values of dtype, 16-byte aligned), freq: device, 4
+ * doubles or NULL (1/4 each).  scalers: ONE device block holding nsc scaler
+ * rows, row j at scalers + j*stride bytes (stride >= n): point
+ * plfx_traverse_psr's scalers[j] into it.  nsc == 0 (scalers may be NULL)
+ * gives plfx_root_lnl_psr's site_lnl bit for bit.  Asynchronous, no
+ * workspace, capture-safe.  PLFX_ERR_INVALID before any launch: a bad dtype,
+ * n < 0, a NULL or misaligned x, a NULL site_lnl, nsc < 0, nsc > 0 with NULL
+ * scalers, stride < n.  n == 0 launches nothing. */
+int plfx_site_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const uint8_t *scalers, int nsc, int64_t stride, double *site_lnl, void *stream);
+
+/* The rate scan: for each of ncand candidate rates r_k, the per-site lnL of
+ * the whole tree with EVERY site at rate r_k; per site the best candidate.
+ *   all_lnl[k*n + i] = lnL of site i under r_k (scaling correction included)
+ *   best_idx[i] = the k of the largest all_lnl[k*n + i] (ties: the lowest k;
+ *                 a NaN never wins; all NaN: 0), best_lnl[i] = that value
+ *                 (-inf if none won), out_lnl = sum_i wgt_i * best_lnl[i]
+ *                 (plfx_root_lnl's fixed-order reduction).
+ * ops, tips, nslots (HOST arrays) as in plfx_traverse_psr; the root is the
+ * parent of the last op.  Every slot an op reads must be a coded tip
+ * (tips[s] != NULL) or the parent of an earlier op: a dense leaf gives
+ * PLFX_ERR_UNSUPPORTED.  blen: device, 2*npmats doubles, branches 2m and 2m+1
+ * of pair m; eigen as plfx_pmatrix; EV, tipvec (required) in the eigen
+ * convention; freq: device root weights (4 doubles, plfx_model_root_weights
+ * in the eigen convention) or NULL; cand_rates: device, ncand doubles, 1 <=
+ * ncand <= PLFX_PSR_SCAN_MAX_RATES; wgt: device int32[n] or NULL (used for
+ * out_lnl only).  Outputs, all device: best_idx int32[n], best_lnl double[n],
+ * all_lnl double[ncand*n] or NULL, out_lnl one double or NULL.
+ * Mechanism: `group` (1..PLFX_PSR_MAX_CATS) candidates are evaluated per
+ * traversal, as the categories of a "virtual alignment" of group*n sites
+ * (virtual site g*n + i = site i under candidate g).  The tip codes and the
+ * category bytes are tiled once; then per pass of gc = min(group, candidates
+ * left): plfx_pmatrix (EIGEN, ncat = gc) into the workspace, the
+ * plfx_traverse_psr launches over gc*n virtual sites with every op's scaler
+ * row, and one kernel that forms the per-site lnL and updates the running
+ * best.  group sizes the workspace and the launches and nothing else: every
+ * output has the same bits for every group and for either PLFX_FUSE setting,
+ * and row k of all_lnl is what plfx_traverse_psr (rate_cat all k) +
+ * plfx_site_lnl_psr give.
+ * workspace: one device block, 256-byte aligned, of at least
+ * plfx_psr_rate_scan_workspace(dtype, nops, ntips, npmats, n, group) bytes,
+ * ntips the number of non-NULL tips[]; its contents are scratch.
+ * Asynchronous, allocates nothing, legal on a capturing stream under
+ * plfx_root_lnl_psr's workspace rules.  Every check runs before the first
+ * launch: the op-list checks of plfx_traverse_psr, the ranges above, NULL
+ * pointers, the workspace's alignment and size (PLFX_ERR_INVALID).  n == 0
+ * launches nothing and zeroes out_lnl if given. */
+#define PLFX_PSR_SCAN_MAX_RATES 1024
+int plfx_psr_rate_scan(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops,
+                       const uint8_t *const *tips, int nslots, const double *blen, int npmats,
+                       const double *eigen, const void *EV, const void *tipvec, const double *cand_rates,
+                       int ncand, int group, const double *freq, const int32_t *wgt, int64_t n,
+                       void *workspace, size_t workspace_bytes, int32_t *best_idx, double *best_lnl,
+                       double *all_lnl, double *out_lnl, void *stream);
+
+/* Host only.  *bytes = the size of the scan's workspace, the sum of these
+ * parts, each array rounded up to 256 bytes: nops CLVs of group*n*4 values of
+ * dtype, ntips code arrays of group*n bytes, nops scaler rows of group*n
+ * bytes, group*n category bytes, 2*npmats*group*16 matrix values.
+ * PLFX_ERR_INVALID for a bad dtype, a negative count or n, group outside
+ * 1..PLFX_PSR_MAX_CATS or a NULL bytes. */
+int plfx_psr_rate_scan_workspace(int dtype, int nops, int ntips, int npmats, int64_t n, int group,
+                                 size_t *bytes);
+
+/* Host only, no context: from the scan's best_idx to rate_cat and the category
+ * rates.  w_i = wgt ? wgt[i] : 1; W_k = the sum of w_i over the sites with
+ * best_idx[i] == k; used = the candidates some site chose (a site of weight 0
+ * counts).  kept = used if it has at most max_cats members, else its max_cats
+ * members of largest W_k (ties: the lower k).  Categories are numbered by
+ * ascending cand_rates[k] over kept (ties: by k).  A site whose candidate is
+ * kept gets that category; any other site the kept category whose rate is
+ * nearest to its candidate's, |cand_rates[best_idx[i]] - cand_rates[kept]|
+ * (ties: the lower category).  *scale = (sum_i w_i) / (sum_i w_i * rate_i),
+ * both sums in f64 in site order, and cat_rates[c] = cand_rates[kept_c] *
+ * *scale: the weighted mean rate is 1.  rate_cat: uint8[n]; cat_rates:
+ * max_cats doubles, entries from *ncat on are not written.
+ * PLFX_ERR_INVALID (nothing written): a NULL pointer other than wgt, n < 1,
+ * ncand < 1, max_cats outside 1..PLFX_PSR_MAX_CATS, an index outside [0,
+ * ncand), a candidate that is not finite and > 0, a negative weight, a weight
+ * sum of 0.  Deterministic. */
+int plfx_psr_categorize(const double *cand_rates, int ncand, const int32_t *best_idx, const int32_t *wgt,
+                        int64_t n, int max_cats, uint8_t *rate_cat, double *cat_rates, int *ncat,
+                        double *scale);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
