@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "ticket_sum.hpp"
+
 namespace plfx {
 namespace dev {
 
@@ -65,23 +67,19 @@ struct Num<double> {
 // Workspace (kWsWords int64, zero at rest, restored to zero by the last
 // arrivals): slot[s] at ws[s*16] (one 128-B line each, s = blockIdx % kSlots)
 // and top at ws[kSlots*16].  Every add carries its own arrival count:
-// word += kTick + partial, so after A arrivals word = A*kTick + sum and the
-// count decodes as round(word / kTick) whenever |any partial sum| < kTick/2.
+// word += kTick + partial, so after A arrivals word = A*kTick + S and the
+// count decodes as floor((word + kTick/2) / kTick): exact for every running
+// sum S with -2^40 <= S <= 2^40 - 1, one too many at S = 2^40, one too few at
+// S = -2^40 - 1 (ticket_sum.hpp holds this arithmetic; tests/test_ticket_sum.py
+// replays the protocol on the CPU at both ends of the range).
 // Each block makes ONE returned atomic on its slot; the last arrival of a slot
 // makes ONE returned atomic on top; the last arrival there knows the total.
 // Two dependent round trips instead of a count+sum+acquire chain, and at most
 // ceil(G/kSlots) arrivals serialise on a word (~12 ns each, MI355X_MICROARCH.md
-// row fanin).  Precondition: sum |wgt| < 2^40 (the reference's own
-// scalerIncrement is an int).
-constexpr int kSlots = 32;
+// row fanin).  Precondition: sum |wgt| < 2^40, which keeps every running sum
+// inside that range (the reference's own scalerIncrement is an int).
 constexpr int kWsWords = (kSlots + 1) * 16;
-constexpr long long kTick = 1ll << 41;
 
-__device__ __forceinline__ long long decode_count(long long word) {
-  return (word + (kTick >> 1)) >> 41;  // floor((word + kTick/2) / kTick)
-}
-
-// The two round trips for one block total `tot` (one thread).
 // Site weight, loaded unconditionally: wgt == nullptr (all weights 1) reads a
 // dummy word instead of branching round the load.  A load inside a branch got
 // its value sign-extended inside the branch, i.e. an s_waitcnt vmcnt(0) right
@@ -92,21 +90,22 @@ __device__ __forceinline__ int wgt_at(const int32_t *wgt, int64_t site, const vo
   return wgt ? v : 1;
 }
 
+// The two round trips for one block total `tot` (one thread).
 __device__ inline void ticket_publish(long long tot, unsigned long long *wsu, int64_t *out) {
   long long *ws = reinterpret_cast<long long *>(wsu);
   const long long G = gridDim.x;
-  const long long slot = blockIdx.x % kSlots;
-  const long long nslots = G < kSlots ? G : kSlots;
-  const long long arrivals = (G - slot + kSlots - 1) / kSlots;
-  const long long old = __hip_atomic_fetch_add(ws + slot * 16, kTick + tot, __ATOMIC_RELAXED,
+  const long long slot = ticket_slot<unsigned>(blockIdx.x);
+  const long long nslots = ticket_nslots(G);
+  const long long arrivals = ticket_arrivals(G, slot);
+  const long long old = __hip_atomic_fetch_add(ws + slot * 16, ticket_add(tot), __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_AGENT);
   if (decode_count(old) != arrivals - 1) return;
-  const long long slot_sum = old + kTick + tot - arrivals * kTick;
+  const long long slot_sum = ticket_sum_of(old, tot, arrivals);
   __hip_atomic_store(ws + slot * 16, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const long long told = __hip_atomic_fetch_add(ws + kSlots * 16, kTick + slot_sum, __ATOMIC_RELAXED,
+  const long long told = __hip_atomic_fetch_add(ws + kSlots * 16, ticket_add(slot_sum), __ATOMIC_RELAXED,
                                                 __HIP_MEMORY_SCOPE_AGENT);
   if (decode_count(told) != nslots - 1) return;
-  if (out) *out = (int64_t)(told + kTick + slot_sum - nslots * kTick);
+  if (out) *out = (int64_t)ticket_sum_of(told, slot_sum, nslots);
   __hip_atomic_store(ws + kSlots * 16, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

@@ -65,9 +65,9 @@ __device__ __forceinline__ bool lnl_finish(double (&acc)[N], double *partials, u
     // two-level election (a single counter serialises ~12 ns per arrival:
     // 20 us for 1800 blocks): slot counters 128 B apart, then a top counter;
     // both return to zero
-    const unsigned long long G = gridDim.x, slot = blockIdx.x % kSlots;
-    const unsigned long long nslots = G < kSlots ? G : kSlots;
-    const unsigned long long arrivals = (G - slot + kSlots - 1) / kSlots;
+    const unsigned long long G = gridDim.x, slot = ticket_slot<unsigned>(blockIdx.x);
+    const unsigned long long nslots = ticket_nslots(G);
+    const unsigned long long arrivals = ticket_arrivals(G, slot);
     int is_last = 0;
     if (__hip_atomic_fetch_add(ticket + slot * 16, 1ull, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1) {

@@ -345,7 +345,7 @@ int plf_host(plfx_ctx *ctx, const T *x1, const T *x2, T *x3, const T *EV, int n,
   if (n < 0) return fail(ctx, PLFX_ERR_INVALID, "n < 0 (%d)", n);
   if (n > 0 && (!x1 || !x2 || !x3 || !EV || !left || !right))
     return fail(ctx, PLFX_ERR_INVALID, "null argument");
-  if (wgt && n >= 512) {  // the reduction's bound (plfx.h): sum |wgt| < 2^40
+  if (wgt && n >= 512) {  // the reduction's bound (plfx.h): sum |wgt| < 2^40; 511 weights cannot reach it
     int64_t tot = 0;
     for (int i = 0; i < n; i++) tot += wgt[i] < 0 ? -(int64_t)wgt[i] : (int64_t)wgt[i];
     if (tot >= (int64_t(1) << 40)) return fail(ctx, PLFX_ERR_INVALID, "sum |wgt| >= 2^40");
@@ -402,6 +402,8 @@ int plf_host(plfx_ctx *ctx, const T *x1, const T *x2, T *x3, const T *EV, int n,
   PLFX_HIP(ctx, hipStreamSynchronize(s2));
   int64_t sum = 0;
   for (int i = 0; i < used; i++) sum += sums[i];
+  // plf()'s int: the exact sum modulo 2^32 as a signed 32-bit value (plfx.h), as the reference's own
+  // int accumulation wraps
   if (scalerIncrement) *scalerIncrement = (int)sum;
   return PLFX_OK;
 }

@@ -81,10 +81,15 @@
  * waves that run ahead take more of the alignment instead of a fixed share
  * (every site is computed the same way, so results do not change); the queue
  * words, like the sums, reset themselves at the end of each launch.
- * The reduction encodes arrival counts next to the sums and needs
+ * The reduction encodes arrival counts next to the sums: a count is read
+ * back exactly for every running sum S of a launch with
+ * -2^40 <= S <= 2^40 - 1 and is off by one at S = 2^40 and at S = -2^40 - 1.
+ * Every running sum is bounded by sum_j |wgt[j]|, so the contract is
  * sum_j |wgt[j]| < 2^40 per launch (the reference's own scalerIncrement is a
- * 32-bit int); the host entry points check this, the device entry points
- * cannot check it cheaply and leave it to the caller.
+ * 32-bit int); the host entry points check this (PLFX_ERR_INVALID, nothing
+ * written; fewer than 512 sites cannot reach the bound), the device entry
+ * points cannot check it cheaply and leave it to the caller.  Inside the
+ * contract every scaler_sum is the exact int64 sum.
  *
  * No allocation happens per call after warm-up (the host entry points keep
  * grow-only staging buffers in the context).  Each workspace also holds the
@@ -181,7 +186,10 @@ int plfx_ctx_streams(const plfx_ctx *ctx);
 /* ---- (1) drop-in for plf(): host arrays, synchronous -------------------- */
 /* Same argument order and meaning as plf() (app/src/plf.h:1-5); `int&` is
  * `int*`.  Copies to the device, runs the fused kernel, copies back.
- * wgt may be NULL (= all ones). */
+ * wgt may be NULL (= all ones).  *scalerIncrement is the exact sum of the
+ * scaled sites' weights reduced modulo 2^32 to a signed 32-bit int (the
+ * reference's `int` accumulation wraps the same way).  sum |wgt| >= 2^40 is
+ * refused with PLFX_ERR_INVALID before anything is copied or written. */
 int plfx_plf_f32(plfx_ctx *ctx, const float *x1_start, const float *x2_start,
                  float *x3_start, const float *EV, int n, const float *left,
                  const float *right, const int *wgt, int *scalerIncrement);

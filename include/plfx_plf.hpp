@@ -11,6 +11,9 @@
 // f32), same "no error return" contract as the reference -- a failure is
 // reported on stderr and aborts, since the reference signature cannot carry a
 // status.  A double overload is provided for the f64 path.
+// scalerIncrement is the exact sum of the scaled sites' weights reduced modulo
+// 2^32 to a signed 32-bit int (the reference's `int` accumulation wraps the
+// same way); sum |wgt| >= 2^40 is a failure (plfx.h).
 #pragma once
 #include <cstdio>
 #include <cstdlib>
