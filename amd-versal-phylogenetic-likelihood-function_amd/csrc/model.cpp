@@ -249,6 +249,18 @@ int plfx_psr_categorize(const double *cand_rates, int ncand, const int32_t *best
   return PLFX_OK;
 }
 
+// plfx.h section 11b: the stable order of the sites by clamped category, a
+// counting sort.  Every argument is checked before anything is written.
+int plfx_psr_site_order(const uint8_t *rate_cat, int64_t n, int ncat, int64_t *perm) {
+  if (!rate_cat || !perm || n < 0 || ncat < 1 || ncat > PLFX_PSR_MAX_CATS) return PLFX_ERR_INVALID;
+  int64_t start[PLFX_PSR_MAX_CATS + 1] = {0};
+  auto cat = [&](int64_t i) { return rate_cat[i] < ncat ? (int)rate_cat[i] : ncat - 1; };
+  for (int64_t i = 0; i < n; i++) start[cat(i) + 1]++;
+  for (int c = 0; c < ncat; c++) start[c + 1] += start[c];
+  for (int64_t i = 0; i < n; i++) perm[start[cat(i)]++] = i;
+  return PLFX_OK;
+}
+
 int plfx_model_ev(int states, int convention, const double *eigen, double *EV) {
   const int S = states;
   if (S < 2 || S > 64 || !EV || (convention != PLFX_PMAT_STATE && convention != PLFX_PMAT_EIGEN))

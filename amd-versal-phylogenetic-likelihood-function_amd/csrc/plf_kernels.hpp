@@ -164,6 +164,18 @@ hipError_t launch_psr_scan_pass(int dtype, const void *x, int64_t n, int gc, con
 hipError_t launch_psr_tile(const PsrTileDescH *tips, int count, int64_t n, int group, uint8_t *cat, int max_blocks,
                            hipStream_t s);
 
+// Protein per-site rate categories (plfx.h section 11b; plf_psr_prot.hpp;
+// defined in plf_psr_prot.hip = libplfx_psr_prot.so, which libplfx.so links):
+// CLVs of n * 20 values, every matrix of ncat * 400, tipvec NULL or 24 x 20
+// values.  The arguments are launch_plf_psr's and launch_root_lnl_psr's.
+hipError_t launch_plf_psr_prot(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
+                               const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n,
+                               const void *tipvec, unsigned long long *ws, int max_blocks, hipStream_t s);
+hipError_t launch_root_lnl_psr_prot(int dtype, const void *x, int64_t n, const double *freq, const int32_t *wgt,
+                                    const int64_t *scaler_sums, int nsums, double *partials,
+                                    unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,
+                                    hipStream_t s);
+
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,
                              hipStream_t s);

@@ -1,0 +1,394 @@
+// plf_psr_prot.hpp -- device code of the protein per-site-rate (PSR, "CAT")
+// mode, plfx.h section 11b: a CLV is x[site*20 + state], n * 20 values, and a
+// site's two 20 x 20 matrices are chosen by its category byte,
+// c = min(rate_cat[site], ncat - 1).
+//
+// Node update, plf()'s loop with one category and no contraction:
+//   umpL[k]  = sum_l x1[i][l] * left[c*400 + k*20 + l]   (from +0.0, ascending l)
+//   x3[i][l] = sum_k (umpL[k] * umpR[k]) * EV[20k + l]   (from +0.0, ascending k)
+// then the 2^-32 rescale over the site's twenty values.
+//
+// The DNA kernel (plf_psr.hpp) stages both matrix tables in LDS and every lane
+// reads its category's rows.  That does not carry over: 32 categories x 2
+// sides x 400 f64 are 200 KB.  The matrices stay what they are in the Gamma
+// protein kernels (plf_prot_valu.hpp) -- wave-uniform scalar operands -- and
+// the category is made wave-uniform by looping over it:
+//   * one lane owns one site, a wave 64 consecutive sites, a block 4 waves =
+//     256 sites per trip; the waves of a block share nothing but the coded
+//     children's tip table and the final sum, so no trip has a block barrier;
+//   * a dense child's 64 rows reach the lanes through the wave's LDS tile:
+//     coalesced 16-B non-temporal loads, rows of 10 (f64) / 5 (f32) chunks at
+//     an odd chunk stride (11 / 5), so the lanes' ds_read_b128 of their own
+//     rows are conflict-free; a coded child's row is gathered from the 24 x 20
+//     tip table the block stages once (rows at the same odd stride).  The
+//     arithmetic on a gathered row is the dense child's: bit-identical by
+//     construction, with no (category, code) table;
+//   * per side: todo = the lanes whose site is < n; while todo != 0, c = the
+//     category of todo's first lane (a scalar), the lanes of that category run
+//     the twenty dot products against P + c*400 (scalar loads, SGPR operands,
+//     the chains of plf_prot_valu.hpp's exact mode) and leave todo;
+//   * phase 3 (EV, wave-uniform) runs once for all lanes; the scale test is
+//     the lane's own twenty values; x3 leaves through the tile, coalesced.
+// A wave whose 64 sites share a category makes one pass per side, a wave with
+// k distinct categories k: correct for any site order, fast for sites sorted
+// by category (plfx_psr_site_order).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#define PLFX_SECONDARY_TU  // plf_dna.hpp's non-template kernel lives in plf_kernels.hip
+#include "plf_lnl.hpp"
+#include "plf_prot.hpp"
+
+namespace plfx {
+namespace dev {
+
+constexpr int kPsrProtMaxCats = 32;  // PLFX_PSR_MAX_CATS (asserted in plfx_api.hip)
+
+__device__ __forceinline__ int psr_prot_cat(int byte, int ncat) { return byte < ncat ? byte : ncat - 1; }
+
+template <typename T>
+struct PsrProtTile {
+  static constexpr int kChunksPerSite = 20 * (int)sizeof(T) / 16;  // 10 (f64) / 5 (f32)
+  static constexpr int kStride = kChunksPerSite | 1;               // odd: 11 / 5
+  static constexpr int kChunks = 64 * kStride;                     // of one wave's tile
+  static constexpr int kTabChunks = kProtCodes * kStride;          // of the tip table
+  using V = std::conditional_t<sizeof(T) == 8, f64x2, f32x4>;
+};
+
+// The waves of a block work on their own tiles: what orders a wave's LDS
+// writes before the reads of its other lanes is the wave's own program order,
+// which this keeps the compiler from changing.
+__device__ __forceinline__ void psr_prot_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The wave's 64 rows from wbase on into its tile: chunk j = lane + 64 i is
+// site j / kChunksPerSite's chunk j % kChunksPerSite, all loads issued before
+// the first LDS write.  The chunks of sites past n are zero (never used).
+template <typename T>
+__device__ __forceinline__ void psr_prot_tile_load(const T *__restrict__ g, int64_t wbase, int64_t n, int lane,
+                                                   typename PsrProtTile<T>::V *tile) {
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  const V *src = reinterpret_cast<const V *>(g) + wbase * PT::kChunksPerSite + lane;
+  V v[PT::kChunksPerSite];
+  if (wbase + 64 <= n) {
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) v[i] = __builtin_nontemporal_load(src + 64 * i);
+  } else {
+    const int lim = (int)(n - wbase) * PT::kChunksPerSite;  // chunks of valid sites
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) {
+      v[i] = V{};
+      if (lane + 64 * i < lim) v[i] = __builtin_nontemporal_load(src + 64 * i);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < PT::kChunksPerSite; i++) {
+    const int j = lane + 64 * i, s = j / PT::kChunksPerSite, q = j - s * PT::kChunksPerSite;
+    tile[s * PT::kStride + q] = v[i];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void psr_prot_tile_store(T *__restrict__ g, int64_t wbase, int64_t n, int lane,
+                                                    const typename PsrProtTile<T>::V *tile) {
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  V *dst = reinterpret_cast<V *>(g) + wbase * PT::kChunksPerSite + lane;
+  V v[PT::kChunksPerSite];
+#pragma unroll
+  for (int i = 0; i < PT::kChunksPerSite; i++) {
+    const int j = lane + 64 * i, s = j / PT::kChunksPerSite, q = j - s * PT::kChunksPerSite;
+    v[i] = tile[s * PT::kStride + q];
+  }
+  if (wbase + 64 <= n) {
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) __builtin_nontemporal_store(v[i], dst + 64 * i);
+  } else {
+    const int lim = (int)(n - wbase) * PT::kChunksPerSite;
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++)
+      if (lane + 64 * i < lim) __builtin_nontemporal_store(v[i], dst + 64 * i);
+  }
+}
+
+// a row of 20 values at an LDS chunk address <-> registers
+template <typename T>
+__device__ __forceinline__ void psr_prot_row_read(const typename PsrProtTile<T>::V *r, T (&v)[20]) {
+  constexpr int kVals = 16 / (int)sizeof(T);
+#pragma unroll
+  for (int i = 0; i < PsrProtTile<T>::kChunksPerSite; i++) {
+    const typename PsrProtTile<T>::V t = r[i];
+#pragma unroll
+    for (int e = 0; e < kVals; e++) v[i * kVals + e] = t[e];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void psr_prot_row_write(typename PsrProtTile<T>::V *r, const T (&v)[20]) {
+  constexpr int kVals = 16 / (int)sizeof(T);
+#pragma unroll
+  for (int i = 0; i < PsrProtTile<T>::kChunksPerSite; i++) {
+    typename PsrProtTile<T>::V t;
+#pragma unroll
+    for (int e = 0; e < kVals; e++) t[e] = v[i * kVals + e];
+    r[i] = t;
+  }
+}
+
+// fn(k, sum_l x[l] * P[k][l]) for the twenty rows k: plf()'s separate multiply
+// and add from +0.0 (kept: +0.0 + -0.0 is +0.0), ascending l; P is
+// wave-uniform (scalar loads, SGPR operands), kRows chains side by side and
+// kCols columns of operands loaded ahead, as plf_prot_valu.hpp's exact mode.
+// The matrix is read through a constant-address-space pointer: the node's
+// matrices come from the descriptor, not from a __restrict__ kernel argument,
+// and without this the compiler cannot rule out that a store of the kernel
+// changes them -- it then reads them with 400 vector loads per side and pass
+// instead of scalar ones.  (They are inputs: no launch writes them.)
+template <typename T, int kRows, int kCols, typename F>
+__device__ __forceinline__ void psr_prot_dot(const T *__restrict__ P, const T (&x)[20], F &&fn) {
+  constexpr int S = 20;
+  static_assert(S % kRows == 0 && S % kCols == 0, "row groups and column chunks divide 20");
+  using CP = const T __attribute__((address_space(4))) *;
+#pragma unroll
+  for (int gk = 0; gk < S / kRows; gk++) {
+    const CP G = reinterpret_cast<CP>(reinterpret_cast<uintptr_t>(P + gk * kRows * S));
+    T u[kRows], cur[kRows][kCols], nxt[kRows][kCols];
+#pragma unroll
+    for (int j = 0; j < kRows; j++)
+#pragma unroll
+      for (int q = 0; q < kCols; q++) cur[j][q] = G[j * S + q];
+#pragma unroll
+    for (int lc = 0; lc < S; lc += kCols) {
+      if (lc + kCols < S) {
+#pragma unroll
+        for (int j = 0; j < kRows; j++)
+#pragma unroll
+          for (int q = 0; q < kCols; q++) nxt[j][q] = G[j * S + lc + kCols + q];
+      }
+#pragma unroll
+      for (int q = 0; q < kCols; q++) {
+        T pr[kRows];
+#pragma unroll
+        for (int j = 0; j < kRows; j++) pr[j] = x[lc + q] * cur[j][q];
+        pin_chains(pr);
+#pragma unroll
+        for (int j = 0; j < kRows; j++) u[j] = (lc + q == 0 ? T(0) : u[j]) + pr[j];
+      }
+      pin_chains(u);
+#pragma unroll
+      for (int j = 0; j < kRows; j++)
+#pragma unroll
+        for (int q = 0; q < kCols; q++) cur[j][q] = nxt[j][q];
+    }
+#pragma unroll
+    for (int j = 0; j < kRows; j++) fn(gk * kRows + j, u[j]);
+  }
+}
+
+// One side of a node for the wave's 64 sites: every lane of `valid` gets
+// fn(k, ump[k]) exactly once, from the pass of its own category.
+template <typename T, typename F>
+__device__ __forceinline__ void psr_prot_side(const T *__restrict__ P, const T (&x)[20], int cat,
+                                              unsigned long long valid, bool mine_valid, F &&fn) {
+  unsigned long long todo = valid;
+  while (todo) {
+    const int first = __builtin_ctzll(todo);
+    const int c = __builtin_amdgcn_readlane(cat, first);
+    const bool mine = mine_valid && cat == c;
+    // Inside the branch cat == c, and the compiler would replace the scalar c
+    // by the lane's cat: the matrix address would be a vector, its reads
+    // vector loads.  The empty asm keeps c a scalar of its own.
+    int cs = c;
+    asm volatile("" : "+s"(cs));
+    if (mine) psr_prot_dot<T, 4, 2>(P + cs * 400, x, fn);
+    todo &= ~__ballot(mine);
+  }
+}
+
+// One node: x1 / x2 name the uint8 codes of a coded child (T1 / T2).  The
+// pointers are __restrict__ parameters, so that the matrices stay scalar loads
+// after the first store of a trip.
+template <typename T, bool kSum, bool T1, bool T2>
+__device__ __forceinline__ void psr_prot_body(const void *__restrict__ c1, const void *__restrict__ c2,
+                                              T *__restrict__ x3, const T *__restrict__ EV,
+                                              const T *__restrict__ left, const T *__restrict__ right,
+                                              const uint8_t *__restrict__ rate_cat, int ncat,
+                                              const int32_t *__restrict__ wgt, uint8_t *__restrict__ scaler,
+                                              int64_t n, unsigned long long *ws, int64_t *scaler_sum,
+                                              const T *__restrict__ tipvec) {
+  constexpr int S = 20, kPh3 = 10;
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  const T *__restrict__ x1 = static_cast<const T *>(c1);
+  const T *__restrict__ x2 = static_cast<const T *>(c2);
+  const uint8_t *__restrict__ tip1 = static_cast<const uint8_t *>(c1);
+  const uint8_t *__restrict__ tip2 = static_cast<const uint8_t *>(c2);
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  __shared__ V tiles[kWavesPerBlock * PT::kChunks];
+  __shared__ V tab[(T1 || T2) ? PT::kTabChunks : 1];
+  V *const tile = tiles + wave * PT::kChunks;
+  if constexpr (T1 || T2) {
+    T *t = reinterpret_cast<T *>(tab);
+    constexpr int kRowVals = PT::kStride * 16 / (int)sizeof(T);
+    for (int e = threadIdx.x; e < kProtCodes * S; e += kBlock) {
+      const int code = e / S, l = e - code * S;
+      t[code * kRowVals + l] = prot_tip_value<T>(tipvec, code, l);
+    }
+    __syncthreads();
+  }
+  const T m = Num<T>::minlik();
+
+  long long acc = 0;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += stride) {
+    const int64_t wbase = base + wave * 64;
+    if (wbase >= n) continue;  // wave-uniform: none of the wave's sites exists
+    const int64_t site = wbase + lane;
+    const bool in = site < n;
+    const int64_t ld = in ? site : n - 1;
+    const int cat = psr_prot_cat(rate_cat[ld], ncat);
+    const int w = kSum ? wgt_at(wgt, ld, ws) : 0;
+    const unsigned long long valid = __ballot(in);
+
+    T U[S];
+    {
+      T a[S];
+      if constexpr (T1) {
+        psr_prot_row_read<T>(tab + prot_code(tip1[ld]) * PT::kStride, a);
+      } else {
+        psr_prot_tile_load<T>(x1, wbase, n, lane, tile);
+        psr_prot_wave_sync();
+        psr_prot_row_read<T>(tile + lane * PT::kStride, a);
+        psr_prot_wave_sync();  // every lane holds its row before the tile is written again
+      }
+      psr_prot_side<T>(left, a, cat, valid, in, [&](int k, T u) { U[k] = u; });
+    }
+    {
+      T b[S];
+      if constexpr (T2) {
+        psr_prot_row_read<T>(tab + prot_code(tip2[ld]) * PT::kStride, b);
+      } else {
+        psr_prot_tile_load<T>(x2, wbase, n, lane, tile);
+        psr_prot_wave_sync();
+        psr_prot_row_read<T>(tile + lane * PT::kStride, b);
+        psr_prot_wave_sync();
+      }
+      psr_prot_side<T>(right, b, cat, valid, in, [&](int k, T u) { U[k] = U[k] * u; });  // umpL[k] * umpR[k]
+    }
+    if (!in) {
+#pragma unroll
+      for (int k = 0; k < S; k++) U[k] = T(0);  // a lane without a site took no part
+    }
+    // phase 3: O[l] = sum_k U[k] * EV[k][l], separate multiply and add, from +0.0
+    T O[S];
+    {
+      T tok = T(0);
+#pragma unroll
+      for (int h = 0; h < S / kPh3; h++) {
+        T v[kPh3];
+#pragma unroll
+        for (int j = 0; j < kPh3; j++) v[j] = T(0);
+#pragma unroll
+        for (int k = 0; k < S; k++) {
+          int so = 0;
+          asm volatile("" : "+s"(so) : "v"(tok));  // EV row k after the previous row's chains
+          const T *er = EV + so + k * S + h * kPh3;
+          T pr[kPh3];
+#pragma unroll
+          for (int j = 0; j < kPh3; j++) pr[j] = U[k] * er[j];
+          pin_chains(pr);
+#pragma unroll
+          for (int j = 0; j < kPh3; j++) v[j] += pr[j];
+          pin_chains(v);
+          tok = v[kPh3 - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < kPh3; j++) O[h * kPh3 + j] = v[j];
+      }
+    }
+    bool sc = in;
+#pragma unroll
+    for (int l = 0; l < S; l++) sc = sc && (Num<T>::abs(O[l]) < m);
+#pragma unroll
+    for (int l = 0; l < S; l++) {
+      const T s = O[l] * Num<T>::two32();  // exact: power-of-two scaling
+      O[l] = sc ? s : O[l];
+    }
+    psr_prot_row_write<T>(tile + lane * PT::kStride, O);
+    if (in) {
+      if (scaler) scaler[site] = (uint8_t)sc;
+      if (kSum) acc += sc ? (long long)w : 0ll;
+    }
+    psr_prot_wave_sync();
+    psr_prot_tile_store<T>(x3, wbase, n, lane, tile);
+    psr_prot_wave_sync();  // the tile is the next trip's
+  }
+  if constexpr (kSum) block_ticket_sum(acc, ws, scaler_sum);
+}
+
+// Up to kMaxBatch nodes per launch, node = blockIdx.y, sharing EV, n, wgt and
+// rate_cat; T1 / T2: child 1 / 2 of every node of the launch is coded (the
+// descriptor's x1 / x2 then point at uint8 codes).  kSum: some node of the
+// launch wants its weighted scaler sum.  Each node has its own ticket region.
+// 3 waves per SIMD: what the f64 tiles of a CU's blocks allow (3 x 45-49 KB of
+// 160 KB), and 168 VGPRs; f32 spills when it is held to the 128 of 4 waves.
+constexpr int kPsrProtMinWaves = 3;
+
+template <typename T, bool kSum, bool T1, bool T2>
+__global__ void __launch_bounds__(kBlock, kPsrProtMinWaves)
+plf_psr_prot_kernel(const NodeBatch nodes, const T *__restrict__ EV, const uint8_t *__restrict__ rate_cat,
+                    int ncat, const int32_t *__restrict__ wgt, int64_t n, unsigned long long *ws,
+                    const T *__restrict__ tipvec) {
+  const NodeDesc &d = nodes.d[blockIdx.y];
+  psr_prot_body<T, kSum, T1, T2>(d.x1, d.x2, static_cast<T *>(d.x3), EV, static_cast<const T *>(d.left),
+                                 static_cast<const T *>(d.right), rate_cat, ncat, wgt, d.scaler, n,
+                                 ws + (size_t)blockIdx.y * kWsWords, d.scaler_sum, tipvec);
+}
+
+// Root lnL of a protein PSR CLV: L_i = sum_s freq[s] * x[i][s] (from +0.0,
+// ascending s, in f64), one lane per site, its row read as 16-B chunks; the
+// sum over the sites through plf_lnl.hpp's fixed-order reduction, as
+// plf_psr.hpp root_lnl_psr_kernel.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+root_lnl_psr_prot_kernel(const T *__restrict__ x, int64_t n, const double *__restrict__ freq,
+                         const int32_t *__restrict__ wgt, const int64_t *__restrict__ scaler_sums, int nsums,
+                         double *partials, unsigned long long *ticket, double *out,
+                         double *__restrict__ site_lnl) {
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  constexpr int kVals = 16 / (int)sizeof(T);
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t nlast = n - 1;
+  for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += stride) {
+    const int64_t site = base + threadIdx.x;
+    const int64_t ld = site < n ? site : nlast;
+    const V *row = reinterpret_cast<const V *>(x) + ld * PT::kChunksPerSite;
+    V v[PT::kChunksPerSite];
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) v[i] = __builtin_nontemporal_load(row + i);
+    const int w = wgt_at(wgt, ld, partials);
+    double L = 0.0;
+#pragma unroll
+    for (int s = 0; s < 20; s++) L += (freq ? freq[s] : 0.05) * (double)v[s / kVals][s % kVals];
+    if (site < n) {
+      const double l = log(L);
+      if (site_lnl) site_lnl[site] = l;
+      acc += (double)w * l;
+    }
+  }
+  lnl_finish(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+}  // namespace dev
+}  // namespace plfx

@@ -518,6 +518,14 @@ int execute_psr(plfx_ctx *ctx, const plfx::PsrLaunchList &l, const plfx::PsrCall
   static_assert(3 * plfx::kMaxTriples <= kWsRegions, "three ticket regions per level pair");
   for (const plfx::PsrLaunch &it : l.items) {
     const bool triples = it.kind == plfx::kPsrTriples;
+    if (c.states == 20) {  // section 11b: node batches only (the lowering emits no level pair)
+      const hipError_t e = triples ? hipErrorInvalidValue
+                                   : plfx::launch_plf_psr_prot(c.dtype, it.tips, &l.nodes[it.first], it.count, c.EV,
+                                                               c.rate_cat, c.ncat, wgt, c.n, tipvec, ws,
+                                                               ctx->max_blocks, s);
+      if (e != hipSuccess) return hip_fail(ctx, e, "plf_psr protein launch");
+      continue;
+    }
     const hipError_t e =
         triples ? plfx::launch_plf_psr_triples(c.dtype, it.tips, &l.triples[it.first], it.count, c.EV, c.rate_cat,
                                                c.ncat, wgt, c.n, tipvec, ws, ctx->max_blocks, s)
@@ -1157,13 +1165,13 @@ int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *con
 
 // ---- (11) per-site rate categories ----
 
-int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
+// The three entry points for `states` 4 (this section) and 20 (section 11b).
+static int psr_nodes(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count, const void *EV,
                      int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
                      void *stream) {
-  PLFX_BIND(ctx);
   static_assert(PLFX_PSR_MAX_CATS <= 256, "a category is one byte");
   std::string err;
-  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat};
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states};
   if (plfx::lower_psr(call, nodes, count, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   hipStream_t s = pick(stream);
@@ -1172,21 +1180,21 @@ int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int c
   return execute_psr(ctx, ctx->psr_lowered, call, wgt, tipvec, s, w->ws);
 }
 
-int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
-                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
-                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
-                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_traverse(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops, void *const *clv,
+                        const uint8_t *const *tips, int nslots, const void *pmats, int npmats, const void *EV,
+                        int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, uint8_t *const *scalers,
+                        int64_t *scaler_sums, const void *tipvec, void *stream) {
   for (int &c : ctx->sched) c = 0;
   if (nops < 0 || (nops > 0 && (!ops || !clv))) return fail(ctx, PLFX_ERR_INVALID, "bad traverse_psr arguments");
-  // level pairs alone: the deeper passes of entries 0..3 of the schedule are not built for PSR
+  // level pairs alone: the deeper passes of entries 0..3 of the schedule are not built for PSR;
+  // with 20 states there is no level pair either, whatever PLFX_FUSE says
   plfx::TravPlan plan;
-  if (int rc = plan_call(ctx, ops, nops, tips, nslots, npmats, 4, std::min(ctx->psr_fuse, 1), &plan); rc != PLFX_OK)
-    return rc;
+  const int fuse = states == 4 ? std::min(ctx->psr_fuse, 1) : 0;
+  if (int rc = plan_call(ctx, ops, nops, tips, nslots, npmats, states, fuse, &plan); rc != PLFX_OK) return rc;
   // lower: the call, every op and every level pair checked, every descriptor
   // filled, before the first launch
   const plfx::TravArrays arrays{ops, nops, clv, tips, pmats, scalers, scaler_sums};
-  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat};
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states};
   std::string err;
   if (plfx::lower_psr_traversal(plan, arrays, call, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
@@ -1200,10 +1208,9 @@ int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nop
   return publish_sched(ctx, plan, ctx->psr_lowered.launches());
 }
 
-int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
-                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
-                      double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_root_lnl(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                        const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                        double *site_lnl, void *stream) {
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (int rc = check_sums_args(ctx, "root_lnl_psr", out_lnl && n >= 0 && (n == 0 || x), scaler_sums, nsums);
       rc != PLFX_OK)
@@ -1215,10 +1222,69 @@ int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const 
     if (rc != PLFX_OK || nsums == 0) return rc;
   }
   PLFX_WS(ctx, s, w);
-  hipError_t e = plfx::launch_root_lnl_psr(dtype, x, n, freq, wgt, scaler_sums, nsums, w->lnl_partials,
-                                           w->lnl_ticket, out_lnl, site_lnl, ctx->max_blocks, s);
+  const auto launch = states == 4 ? plfx::launch_root_lnl_psr : plfx::launch_root_lnl_psr_prot;
+  hipError_t e = launch(dtype, x, n, freq, wgt, scaler_sums, nsums, w->lnl_partials, w->lnl_ticket, out_lnl,
+                        site_lnl, ctx->max_blocks, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "root_lnl_psr launch");
   return PLFX_OK;
+}
+
+int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
+                     int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
+                     void *stream) {
+  PLFX_BIND(ctx);
+  return psr_nodes(ctx, dtype, 4, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
+}
+
+int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
+                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_traverse(ctx, dtype, 4, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat, ncat, wgt,
+                      scalers, scaler_sums, tipvec, stream);
+}
+
+int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                      double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_root_lnl(ctx, dtype, 4, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
+}
+
+// ---- (11b) the same with a state count: 4 is section 11, 20 the protein kernels ----
+
+static int check_psr_states(plfx_ctx *ctx, int states) {
+  if (states != 4 && states != 20)
+    return fail(ctx, PLFX_ERR_UNSUPPORTED, "per-site rate categories: states=%d not built (4, 20)", states);
+  return PLFX_OK;
+}
+
+int plfx_plf_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count,
+                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                         const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_nodes(ctx, dtype, states, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
+}
+
+int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
+                          void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
+                          int npmats, const void *EV, int64_t n, const uint8_t *rate_cat, int ncat,
+                          const int32_t *wgt, uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
+                          void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_traverse(ctx, dtype, states, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat, ncat, wgt,
+                      scalers, scaler_sums, tipvec, stream);
+}
+
+int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                          const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                          double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_root_lnl(ctx, dtype, states, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
 }
 
 int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,

@@ -33,6 +33,7 @@ int refuse(PsrLaunchList *out, std::string *err, const Prefix &who, const char *
 const char *check_call(const PsrCall &c, const char *own, bool none, bool *run) {
   *run = false;
   if (c.dtype != PLFX_F32 && c.dtype != PLFX_F64) return "bad dtype";
+  if (c.states != 4 && c.states != 20) return "states must be 4 or 20";
   if (c.ncat < 1 || c.ncat > PLFX_PSR_MAX_CATS) return "ncat outside 1..PLFX_PSR_MAX_CATS";
   if (c.n < 0) return "n < 0";
   if (own) return own;
@@ -72,7 +73,7 @@ int lower_psr(const PsrCall &call, const plfx_psr_node *nodes, int count, PsrLau
     return refuse(out, err, kBatch, f);
   if (!run) return PLFX_OK;
 
-  const size_t cb = psr_clv_bytes(call.dtype, call.n);
+  const size_t cb = psr_clv_bytes(call.dtype, call.n, call.states);
   std::vector<NodeDescH> nb[4];
   for (int i = 0; i < count; i++) {
     const plfx_psr_node &d = nodes[i];
@@ -99,14 +100,16 @@ int lower_psr_traversal(const TravPlan &plan, const TravArrays &t, const PsrCall
   if ((int)plan.level.size() != t.nops || (int)plan.fused.size() != t.nops)
     return refuse(out, err, kTrav, "the plan is not this op list's");
 
-  const size_t cb = psr_clv_bytes(call.dtype, call.n), tb = (size_t)call.n;
-  const size_t mat_bytes = (size_t)call.ncat * 16 * (call.dtype == PLFX_F32 ? 4 : 8);
+  const size_t cb = psr_clv_bytes(call.dtype, call.n, call.states), tb = (size_t)call.n;
+  const size_t mat_bytes = (size_t)call.ncat * call.states * call.states * (call.dtype == PLFX_F32 ? 4 : 8);
+  const bool pairs = call.states == 4;  // the fused level pair exists for 4 states only
   for (int j = 0; j < t.nops; j++) {
     const OpNode d = op_node(t, mat_bytes, j);
     if (const char *f = check_node(d.nd, d.t1, d.t2, cb, tb)) return refuse(out, err, kTrav, f, j);
   }
   // every triple: three outputs written and four leaves read by one launch
   for (const TravGroup &g : plan.groups) {
+    if (!pairs) break;
     if (g.kind != kTravTriple || g.ops.size() != 3 || g.tips < 0 || g.tips > 2)
       return refuse(out, err, kTrav, "the plan holds a fused group other than a level pair");
     const OpNode A = op_node(t, mat_bytes, g.ops[0]), B = op_node(t, mat_bytes, g.ops[1]);
@@ -129,7 +132,7 @@ int lower_psr_traversal(const TravPlan &plan, const TravArrays &t, const PsrCall
     for (auto &v : tb3) v.clear();
     for (auto &v : nb) v.clear();
     for (const TravGroup &g : plan.groups) {
-      if (g.level != lv) continue;
+      if (!pairs || g.level != lv) continue;
       const int a = g.ops[0], b = g.ops[1], p = g.ops[2];
       const plfx_node A = tip_first(op_node(t, mat_bytes, a)).nd, B = tip_first(op_node(t, mat_bytes, b)).nd;
       // P's children as op P names them: child1 = A's slot or B's slot
@@ -137,7 +140,7 @@ int lower_psr_traversal(const TravPlan &plan, const TravArrays &t, const PsrCall
       tb3[g.tips].push_back(triple_desc(a_first ? A : B, a_first ? B : A, op_node(t, mat_bytes, p).nd));
     }
     for (int j = 0; j < t.nops; j++) {
-      if (plan.level[j] != lv || plan.fused[j]) continue;
+      if (plan.level[j] != lv || (pairs && plan.fused[j])) continue;
       const OpNode d = op_node(t, mat_bytes, j);
       nb[(d.t1 ? 1 : 0) | (d.t2 ? 2 : 0)].push_back(node_desc(d.nd));
     }

@@ -16,13 +16,16 @@
 
 namespace plfx {
 
-// What the nodes of a call share.
+// What the nodes of a call share.  states: 4 (plfx.h section 11) or 20
+// (section 11b): values per site of a CLV, and states * states per category
+// of a matrix.
 struct PsrCall {
   int dtype;
   int64_t n;
   int ncat;
   const void *EV;
   const uint8_t *rate_cat;
+  int states = 4;
 };
 
 enum PsrLaunchKind {
@@ -53,9 +56,9 @@ struct PsrLaunchList {
   int launches() const { return (int)items.size(); }  // plfx_traverse_schedule's entry 6
 };
 
-// bytes of one PSR CLV: n sites * 4 states * element size
-inline size_t psr_clv_bytes(int dtype, int64_t n) {
-  return (size_t)(n > 0 ? n : 0) * 4 * (dtype == PLFX_F32 ? 4 : 8);
+// bytes of one PSR CLV: n sites * states * element size
+inline size_t psr_clv_bytes(int dtype, int64_t n, int states = 4) {
+  return (size_t)(n > 0 ? n : 0) * (size_t)states * (dtype == PLFX_F32 ? 4 : 8);
 }
 
 // The launches of `count` nodes, in issue order: the kinds dense/dense,
@@ -69,9 +72,11 @@ int lower_psr(const PsrCall &call, const plfx_psr_node *nodes, int count, PsrLau
 // The whole traversal, level by level.  Within a level: its triples by tip
 // kind 0, 1, 2 in launches of at most kMaxTriples, then its unfused ops by
 // kind of children as lower_psr.  Op j's matrices are pmats + (2 * pmat) *
-// ncat * 16 and + (2 * pmat + 1) * ncat * 16 values.  A triple's leaf ops are
-// stored coded child first (tip_first); P's children keep the order op P
-// names them in.  Checks, all before the list holds anything: the call's
+// ncat * states^2 and + (2 * pmat + 1) * ncat * states^2 values.  With 20
+// states there is no fused kernel: the plan's level pairs are ignored, every
+// op is lowered unfused and no kPsrTriples item is emitted.  A triple's leaf
+// ops are stored coded child first (tip_first); P's children keep the order op
+// P names them in.  Checks, all before the list holds anything: the call's
 // (n == 0 gives an empty list here), every op's section-11 node checks, and
 // per triple that none of its three outputs shares a byte with another of
 // them or with one of its four leaves.  Refusals as lower_psr.

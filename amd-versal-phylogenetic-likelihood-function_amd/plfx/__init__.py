@@ -58,6 +58,7 @@ EXPORTS = (
     "plfx_edge_optimize_psr", "plfx_traverse_psr",
     "plfx_edge_optimize_psr_dev", "plfx_edge_sumtable_psr_batch",
     "plfx_site_lnl_psr", "plfx_psr_rate_scan", "plfx_psr_rate_scan_workspace", "plfx_psr_categorize",
+    "plfx_plf_psr_dev_gen", "plfx_traverse_psr_gen", "plfx_root_lnl_psr_gen", "plfx_psr_site_order",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -204,6 +205,11 @@ def load():
                                      i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.plfx_psr_rate_scan_workspace.argtypes = [i32, i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)]
     L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
+    L.plfx_plf_psr_dev_gen.argtypes = [vp, i32, i32, C.POINTER(PsrNode), i32, vp, i64, vp, i32, vp, vp, vp]
+    L.plfx_traverse_psr_gen.argtypes = [vp, i32, i32, C.POINTER(TravOp), i32, C.POINTER(vp), C.POINTER(vp), i32, vp,
+                                        i32, vp, i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
+    L.plfx_root_lnl_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
+    L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
     _lib = L
     return L
 
@@ -811,6 +817,85 @@ class Context:
         self._psr_states(states)
         self._root_lnl(True, states, x, n, out, None, freq, wgt, scaler_sums, site_lnl, stream)
 
+    # -- (11b) per-site rate categories with a state count -------------------
+    @staticmethod
+    def _psr_gen_states(states):
+        if states not in (4, 20):
+            raise PlfxError(ERR_UNSUPPORTED, f"per-site rate categories: states={states} not built (4, 20)")
+        return int(states)
+
+    def plf_psr_gen(self, states, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, stream=None):
+        """plf_psr() with a state count (plfx.h section 11b): states 4 is
+        plf_psr() itself, states 20 the protein node -- CLVs of 20*n values,
+        left / right of ncat * 400, EV of 400, uint8 protein codes (PROT_CODES
+        rows of 20 in tipvec, None = the default table).  Fast when the sites
+        are sorted by category: see psr_site_order()."""
+        import torch
+
+        S = self._psr_gen_states(states)
+        if isinstance(nodes, dict):
+            nodes = [nodes]
+        n, ncat = int(n), int(ncat)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        _tensor(EV, "EV", dt, S * S, contiguous=False)
+        self._psr_cats(rate_cat, n)
+        _check_aux(n, wgt, None, None)
+        arr = (PsrNode * max(1, len(nodes)))()
+        for i, nd in enumerate(nodes):
+            for k in ("x1", "x2", "x3"):
+                _tensor(nd.get(k), k, dt, S * n, optional=True)
+            for k in ("tip1", "tip2"):
+                _tensor(nd.get(k), k, torch.uint8, n, optional=True)
+            for k in ("left", "right"):
+                _tensor(nd.get(k), k, dt, S * S * max(ncat, 0), optional=True)
+            _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
+            arr[i] = PsrNode(*(_ptr(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
+                                                          "scaler", "scaler_sum")))
+        self._check(self._L.plfx_plf_psr_dev_gen(
+            self.h, F32 if dt == torch.float32 else F64, S, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
+            _ptr(wgt), self._tipvec(tipvec, dt, S), self._sh(stream)))
+
+    def traverse_psr_gen(self, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None,
+                         scaler_sums=None, stream=None, tips=None, tipvec=None):
+        """traverse_psr() with a state count (plfx.h section 11b).  With
+        states 20 a CLV slot holds 20*n values, pmats whole (left, right) pairs
+        of ncat * 400 values each, and no level pair is fused whatever
+        PLFX_FUSE says: last_schedule() reports triples 0, unfused = the ops."""
+        import torch
+
+        S = self._psr_gen_states(states)
+        n, ncat = int(n), int(ncat)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        top, nops, slots, tp, nslots, npmats, sc = self._traverse_args(
+            ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, S, S * S * max(ncat, 1), S * S)
+        self._psr_cats(rate_cat, n)
+        self._check(self._L.plfx_traverse_psr_gen(
+            self.h, F32 if dt == torch.float32 else F64, S, top, nops, slots, tp, nslots, _ptr(pmats), npmats,
+            _ptr(EV), n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt, S),
+            self._sh(stream)))
+
+    def root_lnl_psr_gen(self, states, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None,
+                         stream=None):
+        """root_lnl_psr() with a state count (plfx.h section 11b): states
+        values per site, freq None = 1/states each."""
+        import torch
+
+        S = self._psr_gen_states(states)
+        _tensor(out, "out", torch.float64, 1, contiguous=False)
+        _tensor(x, "x", (torch.float32, torch.float64), S * n)
+        for k, t, m in (("freq", freq, S), ("site_lnl", site_lnl, n)):
+            _tensor(t, k, torch.float64, m, optional=True)
+        _check_aux(n, wgt, None, None)
+        _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
+        p = _ptr
+        self._check(self._L.plfx_root_lnl_psr_gen(
+            self.h, F32 if x.dtype == torch.float32 else F64, S, p(x), int(n), p(freq), p(wgt), p(scaler_sums),
+            0 if scaler_sums is None else scaler_sums.numel(), p(out), p(site_lnl), self._sh(stream)))
+
     def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
         """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the
         dense CLV x1 or the uint8 codes tip1 with the eigen-convention table."""
@@ -1149,6 +1234,20 @@ def psr_categorize(cand_rates, best_idx, wgt=None, max_cats=PSR_MAX_CATS):
     _host_check(load().plfx_psr_categorize(rp, r.size, _nptr(idx), _nptr(w), idx.size, max_cats, _nptr(cat), ratesp,
                                            C.byref(ncat), C.byref(scale)), "psr_categorize")
     return cat, rates[:ncat.value].copy(), float(scale.value)
+
+
+def psr_site_order(rate_cat, ncat):
+    """The stable order of the sites by clamped category (plfx.h section 11b,
+    plfx_psr_site_order): an int64 permutation perm with perm[j] = the site
+    that goes to position j.  Apply it to every tip's codes, wgt and rate_cat
+    once, after psr_categorize(): the protein PSR node is fast on sorted
+    sites.  rate_cat: host uint8 array."""
+    cat = np.ascontiguousarray(rate_cat)
+    if cat.dtype != np.uint8 or cat.ndim != 1:
+        raise PlfxError(ERR_INVALID, "rate_cat must be a one-dimensional uint8 array")
+    perm = np.empty(cat.size, np.int64)
+    _host_check(load().plfx_psr_site_order(_nptr(cat), cat.size, int(ncat), _nptr(perm)), "psr_site_order")
+    return perm
 
 
 def model_ev(eigen, states, convention=PMAT_STATE):

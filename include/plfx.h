@@ -596,9 +596,11 @@ int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *con
  * ExaML next to the Gamma model of every section above (extension) ----------
  * Every site belongs to exactly ONE of ncat rate categories, so a PSR CLV is
  * x[site*4 + state] -- n * 4 values, a quarter of the Gamma layout, 16-byte
- * aligned -- and a node's P matrices are chosen per site.  DNA (4 states)
- * only, f32 and f64; there is no states argument (the Python binding answers
- * a protein request with PLFX_ERR_UNSUPPORTED).
+ * aligned -- and a node's P matrices are chosen per site.  DNA (4 states),
+ * f32 and f64; the entry points of this section have no states argument (the
+ * Python binding answers a protein request to them with
+ * PLFX_ERR_UNSUPPORTED).  Section (11b) has the node, the traversal and the
+ * root lnL for protein.
  *   rate_cat: device uint8[n]; site i uses category min(rate_cat[i], ncat-1)
  *             (the clamp of protein tip codes >= 24: no index leaves a table);
  *   ncat:     1 <= ncat <= PLFX_PSR_MAX_CATS, else PLFX_ERR_INVALID;
@@ -772,6 +774,81 @@ typedef struct {
  * checks only and launches nothing. */
 int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges,
                                  int64_t n, const void *tipvec, void *stream);
+
+/* ---- (11b) per-site rate categories for protein: the likelihood half ------
+ * (PROTCAT: the node, a whole traversal, the root lnL; extension).  The three
+ * entry points below are their section-(11) namesakes with a `states`
+ * argument, as plfx_plf_dev_gen stands beside plfx_plf_dev_f64: states == 4 is
+ * section (11) itself (the same kernels, the same bits), states == 20 is the
+ * protein path described here, any other value PLFX_ERR_UNSUPPORTED.  The
+ * branch-length half (the protein versions of plfx_edge_*_psr and of section
+ * 12's rate scan) does not exist yet.
+ * With 20 states a PSR CLV is x[site*20 + state] -- n * 20 values of dtype
+ * (f32 or f64), a quarter of the Gamma protein layout, base 16-byte aligned;
+ *   left, right: ncat * 400 values [c][k][l] -- what plfx_pmatrix(states = 20)
+ *             writes per branch for `ncat` rates;
+ *   rate_cat, the clamp c = min(rate_cat[i], ncat-1) and 1 <= ncat <=
+ *             PLFX_PSR_MAX_CATS as in section (11).
+ * Node update -- plf()'s loop with one category, run on each category's sites
+ * with that category's matrices; no FMA contraction, so exact mode is the
+ * only mode:
+ *   umpL[k]  = sum_l x1[i][l] * left[c*400 + k*20 + l]    from +0.0, ascending l
+ *                                                         (same for right / x2)
+ *   x3[i][l] = sum_k (umpL[k] * umpR[k]) * EV[20k + l]    from +0.0, ascending k
+ * then, if all TWENTY |x3[i][.]| < 2^-32 (strict; NaN never scales), they are
+ * multiplied by 2^32, scaler[i] = 1 and wgt[i] enters the node's scaler sum.
+ * A coded child is as in section (8) protein: uint8 codes, row min(code, 23)
+ * of a 24 x 20 table of dtype, tipvec NULL = the default table of section
+ * (8); results are bit-identical to the dense computation on the expanded
+ * child.
+ *
+ * SITE ORDER.  The kernel makes the category uniform across a wave of 64
+ * consecutive sites by looping: a wave whose 64 sites share one category makes
+ * one pass over its matrices, a wave with k distinct categories k passes.  The
+ * results are the same bits for any order of the sites; the time is not: sort
+ * the site patterns by category once, after plfx_psr_categorize (site patterns
+ * are exchangeable: permute every tip's codes, wgt and rate_cat alike).
+ * plfx_psr_site_order gives the permutation.  DESIGN.md section 3.8b has the
+ * measured cost of unsorted sites. */
+
+/* plfx_plf_psr_dev with a state count: the same plfx_psr_node array, checks
+ * (all before the first launch; the overlap check uses n * states values per
+ * CLV), n == 0 rule, launches of at most 32 nodes of one kind of children
+ * (node = blockIdx.y, a ticket region each), asynchronous, allocates nothing,
+ * descriptors in the kernel arguments, capture-safe.  tipvec: 16 x 4 values
+ * (states 4) or 24 x 20 (states 20), or NULL. */
+int plfx_plf_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count,
+                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                         const void *tipvec, void *stream);
+
+/* plfx_traverse_psr with a state count.  Op j's matrices are left = pmats +
+ * (2*pmat) * ncat * states^2 and right = pmats + (2*pmat + 1) * ncat * states^2
+ * values of dtype.  With states == 20 there is no fused level pair, whatever
+ * PLFX_FUSE says: every level runs as batches by kind of children, and
+ * plfx_traverse_schedule reports entry 4 = 0, entry 5 = nops, entry 6 = the
+ * launches.  Every CLV, scaler byte and scaler_sums[j] is bit-identical to
+ * the ops run one by one as one-node plfx_plf_psr_dev_gen calls. */
+int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
+                          void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
+                          int npmats, const void *EV, int64_t n, const uint8_t *rate_cat, int ncat,
+                          const int32_t *wgt, uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
+                          void *stream);
+
+/* plfx_root_lnl_psr with a state count:
+ *   lnL = sum_i wgt_i * log( sum_s freq[s] * x[i][s] )
+ *         + (sum_{j<nsums} scaler_sums[j]) * log(2^-32)
+ * over `states` values per site, in f64; freq NULL = 1/states each; site_lnl
+ * optional; the fixed-order reduction and the rules of plfx_root_lnl_psr. */
+int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                          const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                          double *site_lnl, void *stream);
+
+/* Host only: perm[j] = the site that goes to position j when the n sites are
+ * sorted by clamped category min(rate_cat[i], ncat-1), stably (sites of one
+ * category keep their order) -- a counting sort.  rate_cat and perm are host
+ * arrays of n entries.  PLFX_ERR_INVALID for a NULL pointer, n < 0 or ncat
+ * outside 1..PLFX_PSR_MAX_CATS; n == 0 writes nothing. */
+int plfx_psr_site_order(const uint8_t *rate_cat, int64_t n, int ncat, int64_t *perm);
 
 /* ---- (12) the PSR rate scan and rate categorisation (extension) -----------
  * Section (11) takes rate_cat and the category rates as inputs; this section
