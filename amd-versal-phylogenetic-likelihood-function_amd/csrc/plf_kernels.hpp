@@ -175,6 +175,24 @@ hipError_t launch_root_lnl_psr_prot(int dtype, const void *x, int64_t n, const d
                                     const int64_t *scaler_sums, int nsums, double *partials,
                                     unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,
                                     hipStream_t s);
+// The branch-length half (plfx.h section 11c): launch_edge_sumtable_psr,
+// _psr_batch, launch_edge_derivatives_psr and launch_edge_optimize_psr for
+// tables of n * 20 values, tipvec 24 x 20 values; n >= 1 for the sum tables.
+hipError_t launch_edge_sumtable_psr_prot(int dtype, bool tip, const void *x1, const void *x2, int64_t n,
+                                         const void *tipvec, void *sumtab, int max_blocks, hipStream_t s);
+hipError_t launch_edge_sumtable_psr_prot_batch(int dtype, bool tip, const PsrEdgeDescH *edges, int count, int64_t n,
+                                               const void *tipvec, int max_blocks, hipStream_t s);
+hipError_t launch_edge_derivatives_psr_prot(int dtype, const void *sumtab, int64_t n, const double *lambda,
+                                            const double *rates, int ncat, const uint8_t *rate_cat,
+                                            const int32_t *wgt, const double *t, const int64_t *scaler_sums,
+                                            int nsums, double *partials, unsigned long long *ticket, double *out3,
+                                            double *site_lnl, int max_blocks, hipStream_t s);
+hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, int count, int64_t n,
+                                         const double *lambda, const double *rates, int ncat,
+                                         const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                         double tmax, int max_evals, void *state, double *partials,
+                                         unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
+                                         int max_blocks, hipStream_t s);
 
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,

@@ -1,6 +1,7 @@
 // plf_psr_prot.hip -- launchers of the protein per-site-rate kernels
 // (plf_psr_prot.hpp: the node and the root lnL with one rate category per site
-// and 20 states, plfx.h section 11b).
+// and 20 states, plfx.h section 11b; the sum table -- one and batched --, the
+// edge sums and the branch-length loop on the device, section 11c).
 //
 // Built into a library of its own, plfx/libplfx_psr_prot.so, which libplfx.so
 // links, as plf_psr.hip and plf_edge.hip are: the code objects of the other
@@ -44,6 +45,24 @@ hipError_t launch_plf_psr_prot_t(const NodeDescH *nodes, int count, const void *
   return p.any_sum ? go(std::true_type{}) : go(std::false_type{});
 }
 
+// The grid of the edge sums, from edge_deriv_psr_prot_kernel's occupancy: one
+// site per lane and trip, capped at the partial slots of lnl_finish.  Also the
+// one-edge grid of the device loop, whose sums then have that kernel's slots
+// and order.
+template <typename T>
+int64_t edge_deriv_psr_prot_grid(int64_t n, int max_blocks) {
+  static int cache = 0;
+  return std::min<int64_t>(
+      grid_x((const void *)&dev::edge_deriv_psr_prot_kernel<T>, cache, n, kBlock, 1, max_blocks), kLnlMaxGrid);
+}
+
+// 16-B chunks of a table of n sites, and those a block of the sum-table kernels covers per trip
+template <typename T>
+int64_t sumtab_chunks(int64_t n) {
+  return n * dev::PsrProtTile<T>::kChunksPerSite;
+}
+constexpr int kSumtabChunksPerTrip = kBlock * 4;
+
 }  // namespace
 
 hipError_t launch_plf_psr_prot(int dtype, int tips, const NodeDescH *nodes, int count, const void *EV,
@@ -72,6 +91,83 @@ hipError_t launch_root_lnl_psr_prot(int dtype, const void *x, int64_t n, const d
             std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks), kLnlMaxGrid);
         return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, freq, wgt, scaler_sums, nsums,
                       partials, ticket, out, site_lnl);
+      },
+      bools{dtype == 1});
+}
+
+hipError_t launch_edge_sumtable_psr_prot(int dtype, bool tip, const void *x1, const void *x2, int64_t n,
+                                         const void *tipvec, void *sumtab, int max_blocks, hipStream_t s) {
+  if (n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64, auto kTip) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::edge_sumtable_psr_prot_kernel<T, kTip()>;
+        const int64_t gx = grid_x((const void *)kernel, cache, sumtab_chunks<T>(n), kSumtabChunksPerTrip, 1, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, x1, (const T *)x2, n, (const T *)tipvec, (T *)sumtab);
+      },
+      bools{dtype == 1}, bools{tip});
+}
+
+hipError_t launch_edge_sumtable_psr_prot_batch(int dtype, bool tip, const PsrEdgeDescH *edges, int count, int64_t n,
+                                               const void *tipvec, int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch || n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64, auto kTip) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::edge_sumtable_psr_prot_batch_kernel<T, kTip()>;
+        const auto p = pack<dev::PsrProtEdgeBatch>(edges, count, [](const PsrEdgeDescH &) { return false; });
+        // an edge's share of the co-resident blocks, as a node's in launch_plf_psr_prot_t
+        const int64_t gx =
+            grid_x((const void *)kernel, cache, sumtab_chunks<T>(n), kSumtabChunksPerTrip, count, max_blocks);
+        return launch(kernel, dim3((unsigned)gx, (unsigned)count), kBlock, s, p.b, n, (const T *)tipvec);
+      },
+      bools{dtype == 1}, bools{tip});
+}
+
+hipError_t launch_edge_derivatives_psr_prot(int dtype, const void *sumtab, int64_t n, const double *lambda,
+                                            const double *rates, int ncat, const uint8_t *rate_cat,
+                                            const int32_t *wgt, const double *t, const int64_t *scaler_sums,
+                                            int nsums, double *partials, unsigned long long *ticket, double *out3,
+                                            double *site_lnl, int max_blocks, hipStream_t s) {
+  if (ncat < 1 || ncat > dev::kPsrProtMaxCats) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        const int64_t gx = edge_deriv_psr_prot_grid<T>(n, max_blocks);
+        return launch(&dev::edge_deriv_psr_prot_kernel<T>, dim3((unsigned)gx), kBlock, s, (const T *)sumtab, n, lambda,
+                      rates, ncat, rate_cat, wgt, t, scaler_sums, nsums, partials, ticket, out3, site_lnl);
+      },
+      bools{dtype == 1});
+}
+
+// The device loop (plf_psr.hip launch_edge_optimize_psr for tables of 20
+// states): max_evals launches of edge_opt_psr_prot_kernel over the group's
+// edges (blockIdx.y); the first of them initialises the per-edge state.  The
+// per-edge grid is the one-edge grid unless the group's 3 * gx * count slots
+// would not fit the 3 * kLnlMaxGrid doubles of `partials`.
+hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, int count, int64_t n,
+                                         const double *lambda, const double *rates, int ncat,
+                                         const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                         double tmax, int max_evals, void *state, double *partials,
+                                         unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
+                                         int max_blocks, hipStream_t s) {
+  if (count < 1 || count > kMaxBatch || ncat < 1 || ncat > dev::kPsrProtMaxCats) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        dev::EdgeOptTabs a{};
+        for (int j = 0; j < count; j++) a.st[j] = sumtabs[j];
+        const int64_t gx = std::max<int64_t>(
+            1, std::min<int64_t>(edge_deriv_psr_prot_grid<T>(n, max_blocks), kLnlMaxGrid / count));
+        for (int i = 0; i < max_evals; i++) {
+          hipError_t e = launch(&dev::edge_opt_psr_prot_kernel<T>, dim3((unsigned)gx, (unsigned)count), kBlock, s, a,
+                                n, lambda, rates, ncat, rate_cat, wgt, t0, tmin, tmax, max_evals, (int)(i == 0),
+                                static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3, evals);
+          if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
       },
       bools{dtype == 1});
 }

@@ -32,6 +32,10 @@
 // A wave whose 64 sites share a category makes one pass per side, a wave with
 // k distinct categories k: correct for any site order, fast for sites sorted
 // by category (plfx_psr_site_order).
+//
+// At the end of the file: the branch-length half (plfx.h section 11c) -- the
+// sum table, one and batched, the three edge sums and the branch-length loop
+// on the device, over tables of n * 20 values.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +43,7 @@
 #include <type_traits>
 
 #define PLFX_SECONDARY_TU  // plf_dna.hpp's non-template kernel lives in plf_kernels.hip
+#include "plf_edge.hpp"
 #include "plf_lnl.hpp"
 #include "plf_prot.hpp"
 
@@ -115,6 +120,40 @@ __device__ __forceinline__ void psr_prot_tile_store(T *__restrict__ g, int64_t w
 #pragma unroll
     for (int i = 0; i < PT::kChunksPerSite; i++)
       if (lane + 64 * i < lim) __builtin_nontemporal_store(v[i], dst + 64 * i);
+  }
+}
+
+// psr_prot_tile_load in two steps, for a loop that keeps its next tile in
+// flight in registers while it works on this one (the edge sums below): the
+// same chunks from the same addresses into v, then v into the tile.
+template <typename T>
+__device__ __forceinline__ void psr_prot_tile_fetch(const T *__restrict__ g, int64_t wbase, int64_t n, int lane,
+                                                    typename PsrProtTile<T>::V (&v)[PsrProtTile<T>::kChunksPerSite]) {
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  const V *src = reinterpret_cast<const V *>(g) + wbase * PT::kChunksPerSite + lane;
+  if (wbase + 64 <= n) {
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) v[i] = __builtin_nontemporal_load(src + 64 * i);
+  } else {
+    const int lim = (int)(n - wbase) * PT::kChunksPerSite;  // chunks of valid sites
+#pragma unroll
+    for (int i = 0; i < PT::kChunksPerSite; i++) {
+      v[i] = V{};
+      if (lane + 64 * i < lim) v[i] = __builtin_nontemporal_load(src + 64 * i);
+    }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void psr_prot_tile_put(
+    const typename PsrProtTile<T>::V (&v)[PsrProtTile<T>::kChunksPerSite], int lane,
+    typename PsrProtTile<T>::V *tile) {
+  using PT = PsrProtTile<T>;
+#pragma unroll
+  for (int i = 0; i < PT::kChunksPerSite; i++) {
+    const int j = lane + 64 * i, s = j / PT::kChunksPerSite, q = j - s * PT::kChunksPerSite;
+    tile[s * PT::kStride + q] = v[i];
   }
 }
 
@@ -388,6 +427,202 @@ root_lnl_psr_prot_kernel(const T *__restrict__ x, int64_t n, const double *__res
     }
   }
   lnl_finish(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+// ---- plfx.h section 11c: the branch-length half ----
+//
+// Sum table of a protein PSR branch: x1 * x2 over n * 20 values, 16-B chunks,
+// 10 (f64) / 5 (f32) per site, U chunks per thread and trip, all of a trip's
+// loads issued before its stores (plf_psr.hpp edge_sumtable_psr_chunks with 20
+// states).  kTip: side 1 is one code per site, x1[i][k] =
+// tipvec[min(code, 23)*20 + k].
+template <typename T, bool kTip>
+__device__ __forceinline__ void edge_sumtable_psr_prot_chunks(const void *__restrict__ x1,
+                                                              const T *__restrict__ x2, int64_t n,
+                                                              const T *__restrict__ tipvec,
+                                                              T *__restrict__ out) {
+  using V = typename PsrProtTile<T>::V;
+  constexpr int kVals = 16 / (int)sizeof(T);
+  constexpr int kSite = PsrProtTile<T>::kChunksPerSite;
+  constexpr int U = 4;
+  const int64_t total = n * kSite;
+  const V *a = static_cast<const V *>(x1);
+  const uint8_t *codes = static_cast<const uint8_t *>(x1);
+  const V *b = reinterpret_cast<const V *>(x2);
+  V *o = reinterpret_cast<V *>(out);
+  const int64_t stride = (int64_t)gridDim.x * (kBlock * U);
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * U); base < total; base += stride) {
+    V va[U], vb[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t j = base + u * kBlock + threadIdx.x;
+      if (j >= total) continue;
+      vb[u] = __builtin_nontemporal_load(b + j);
+      if constexpr (kTip) {
+        const int64_t site = j / kSite;
+        const T *tv = tipvec + prot_code(codes[site]) * 20 + (int)(j - site * kSite) * kVals;
+#pragma unroll
+        for (int e = 0; e < kVals; e++) va[u][e] = tv[e];
+      } else {
+        va[u] = __builtin_nontemporal_load(a + j);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t j = base + u * kBlock + threadIdx.x;
+      if (j < total) __builtin_nontemporal_store(va[u] * vb[u], o + j);
+    }
+  }
+}
+
+template <typename T, bool kTip>
+__global__ void __launch_bounds__(kBlock)
+edge_sumtable_psr_prot_kernel(const void *__restrict__ x1, const T *__restrict__ x2, int64_t n,
+                              const T *__restrict__ tipvec, T *__restrict__ out) {
+  edge_sumtable_psr_prot_chunks<T, kTip>(x1, x2, n, tipvec, out);
+}
+
+// Up to kMaxBatch sum tables per launch, edge = blockIdx.y, all with the same
+// kind of side 1: each edge's table is the one-edge kernel's, chunk for chunk
+// (plf_psr.hpp PsrEdgeBatch; the host's PsrEdgeDescH).
+struct PsrProtEdgeDesc {
+  const void *x1, *x2;
+  void *out;
+};
+struct PsrProtEdgeBatch {
+  PsrProtEdgeDesc d[kMaxBatch];
+};
+
+template <typename T, bool kTip>
+__global__ void __launch_bounds__(kBlock)
+edge_sumtable_psr_prot_batch_kernel(const PsrProtEdgeBatch edges, int64_t n, const T *__restrict__ tipvec) {
+  const PsrProtEdgeDesc &d = edges.d[blockIdx.y];
+  edge_sumtable_psr_prot_chunks<T, kTip>(d.x1, static_cast<const T *>(d.x2), n, tipvec, static_cast<T *>(d.out));
+}
+
+// The three edge sums of a protein PSR branch.  x_k = lambda_k * rates[c_i];
+// the block forms the ncat x 20 factor triples {e, e x, e x x} once from the
+// device t into LDS (edge_factors: the bits of the Gamma and DNA kernels), a
+// category's row as e[0..20), e x[0..20), e x x[0..20): 60 doubles padded to 62
+// = 31 16-B slots, odd, as plf_psr.hpp pads 12 to 14.  One lane owns one site,
+// a wave 64 consecutive sites.  The wave's 64 rows reach the lanes through its
+// LDS tile, as the node's dense children do (coalesced 16-B non-temporal
+// loads, no block barrier in a trip), with the next tile's chunks in flight in
+// registers meanwhile: read straight from global -- one 16-B load per lane at a
+// 160-B lane stride, root_lnl_psr_prot_kernel's way -- the kernel took as long
+// as the Gamma-4 kernel takes for four times the values.
+// A lane reads its category's row two factors at a time; lanes of one category
+// read the same addresses (broadcast), so a wave of category-sorted sites reads
+// without a conflict.  L, L1, L2 = sum_k st[i][k] * {e, e x, e x x} from +0.0,
+// ascending k, in f64; the sums over the sites as plf_edge.hpp's (edge_site,
+// lnl_finish<3>).  Lane and trip of a site are what they were in the direct
+// form, so every sum has the same bits.
+//
+// edge_deriv_psr_prot_sites: the block's factor table at branch length t and
+// its share of the sites into acc (blocks along x): the body of
+// edge_deriv_psr_prot_kernel and of edge_opt_psr_prot_kernel.  partials: only
+// a readable word here (wgt_at's dummy).
+constexpr int kPsrProtFactorStride = 62;
+template <typename T>
+__device__ __forceinline__ void edge_deriv_psr_prot_sites(const T *__restrict__ st, int64_t n,
+                                                          const double *__restrict__ lambda,
+                                                          const double *__restrict__ rates, int ncat,
+                                                          const uint8_t *__restrict__ rate_cat,
+                                                          const int32_t *__restrict__ wgt, const double t,
+                                                          const double *partials, double *__restrict__ site_lnl,
+                                                          double (&acc)[3]) {
+  constexpr int S = 20;
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  static_assert(kPsrProtFactorStride >= 3 * S && kPsrProtFactorStride % 2 == 0 && (kPsrProtFactorStride / 2) % 2 == 1,
+                "a row is whole 16-B slots, an odd number of them");
+  __shared__ __attribute__((aligned(16))) double tab[kPsrProtMaxCats * kPsrProtFactorStride];
+  for (int i = threadIdx.x; i < ncat * S; i += kBlock) {
+    const int c = i / S, k = i - c * S;
+    double e0, e1, e2;
+    edge_factors(lambda[k], rates[c], t, e0, e1, e2);
+    tab[c * kPsrProtFactorStride + k] = e0;
+    tab[c * kPsrProtFactorStride + S + k] = e1;
+    tab[c * kPsrProtFactorStride + 2 * S + k] = e2;
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  __shared__ V tiles[kWavesPerBlock * PT::kChunks];
+  V *const tile = tiles + wave * PT::kChunks;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t nlast = n - 1;
+  int64_t wbase = (int64_t)blockIdx.x * kBlock + wave * 64;  // wave-uniform, as the loop's trip count
+  V pf[PT::kChunksPerSite];
+  if (wbase < n) psr_prot_tile_fetch<T>(st, wbase, n, lane, pf);
+  for (; wbase < n; wbase += stride) {
+    const int64_t site = wbase + lane;
+    const int64_t ld = site < n ? site : nlast;
+    const int cat = rate_cat[ld];
+    const int w = wgt_at(wgt, ld, partials);
+    psr_prot_tile_put<T>(pf, lane, tile);
+    psr_prot_wave_sync();
+    if (wbase + stride < n) psr_prot_tile_fetch<T>(st, wbase + stride, n, lane, pf);
+    T v[S];
+    psr_prot_row_read<T>(tile + lane * PT::kStride, v);
+    psr_prot_wave_sync();  // every lane holds its row before the tile is written again
+    const f64x2 *f = reinterpret_cast<const f64x2 *>(tab + psr_prot_cat(cat, ncat) * kPsrProtFactorStride);
+    double L = 0.0, L1 = 0.0, L2 = 0.0;
+#pragma unroll
+    for (int p = 0; p < S / 2; p++) {
+      const f64x2 f0 = f[p], f1 = f[S / 2 + p], f2 = f[S + p];
+      const double xa = (double)v[2 * p], xb = (double)v[2 * p + 1];
+      L += xa * f0.x;
+      L1 += xa * f1.x;
+      L2 += xa * f2.x;
+      L += xb * f0.y;
+      L1 += xb * f1.y;
+      L2 += xb * f2.y;
+    }
+    if (site < n) {
+      const double l = edge_site(L, L1, L2, w, acc);
+      if (site_lnl) site_lnl[site] = l;
+    }
+  }
+}
+
+// n == 0: one block, out = {correction, 0, 0}.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+edge_deriv_psr_prot_kernel(const T *__restrict__ st, int64_t n, const double *__restrict__ lambda,
+                           const double *__restrict__ rates, int ncat, const uint8_t *__restrict__ rate_cat,
+                           const int32_t *__restrict__ wgt, const double *__restrict__ tp,
+                           const int64_t *__restrict__ scaler_sums, int nsums, double *partials,
+                           unsigned long long *ticket, double *out, double *__restrict__ site_lnl) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  edge_deriv_psr_prot_sites<T>(st, n, lambda, rates, ncat, rate_cat, wgt, *tp, partials, site_lnl, acc);
+  lnl_finish<3>(acc, partials, ticket, out, scaler_sums, nsums);
+}
+
+// The branch-length loop on the device for protein PSR branches
+// (plfx_edge_optimize_psr_dev_gen): plf_psr.hpp's edge_opt_psr_kernel with the
+// site loop above.  One launch = one evaluation of every edge of the group that
+// has not stopped (blockIdx.y = edge, gridDim.x blocks per edge) and one step
+// of its bracket in the thread that holds the edge's totals (edge_opt_entry,
+// edge_opt_step, unchanged).  A stopped edge's blocks return before any
+// barrier, LDS write, partial or ticket.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+edge_opt_psr_prot_kernel(const EdgeOptTabs tabs, int64_t n, const double *__restrict__ lambda,
+                         const double *__restrict__ rates, int ncat, const uint8_t *__restrict__ rate_cat,
+                         const int32_t *__restrict__ wgt, const double *t0, double tmin, double tmax,
+                         int max_evals, int first, EdgeNewtonStep *state, double *partials,
+                         unsigned long long *ws, double *t_opt, double *out3, int32_t *evals) {
+  EdgeNewtonStep *sp = state + blockIdx.y;
+  bool done;
+  const double t = edge_opt_entry(sp, t0, tmin, tmax, first, done);
+  if (done) return;
+  const T *st = static_cast<const T *>(tabs.st[blockIdx.y]);
+  double *part = partials + (size_t)blockIdx.y * 3 * gridDim.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  edge_deriv_psr_prot_sites<T>(st, n, lambda, rates, ncat, rate_cat, wgt, t, part, nullptr, acc);
+  if (lnl_finish<3, false>(acc, part, ws + (size_t)blockIdx.y * kWsWords, nullptr, nullptr, 0))
+    edge_opt_step(sp, acc, t, tmin, tmax, max_evals, first, t_opt, out3, evals);
 }
 
 }  // namespace dev

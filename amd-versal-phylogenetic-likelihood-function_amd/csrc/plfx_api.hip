@@ -1287,54 +1287,54 @@ int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, i
   return psr_root_lnl(ctx, dtype, states, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
 }
 
-int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
-                           int64_t n, const void *tipvec, void *sumtab, void *stream) {
-  PLFX_BIND(ctx);
+// The branch-length half of sections (11) and (11c): states 4 runs plf_psr.hip's
+// launchers, states 20 plf_psr_prot.hip's; the checks, the host loop and the
+// workspace regions are shared.  The callers have bound the context.
+static int psr_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                             const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
-  const int rc = check_sumtable_args(ctx, tip1, x1, x2, n, tipvec, sumtab, plfx::psr_clv_bytes(dtype, n));
+  const int rc = check_sumtable_args(ctx, tip1, x1, x2, n, tipvec, sumtab, plfx::psr_clv_bytes(dtype, n, states));
   if (rc != PLFX_OK || n == 0) return rc;
-  hipError_t e = plfx::launch_edge_sumtable_psr(dtype, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2, n,
-                                                tipvec, sumtab, ctx->max_blocks, pick(stream));
+  const auto launch = states == 4 ? plfx::launch_edge_sumtable_psr : plfx::launch_edge_sumtable_psr_prot;
+  hipError_t e = launch(dtype, tip1 != nullptr, tip1 ? (const void *)tip1 : x1, x2, n, tipvec, sumtab,
+                        ctx->max_blocks, pick(stream));
   if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr launch");
   return PLFX_OK;
 }
 
-int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
-                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
-                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
-                              double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_edge_derivatives(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                                const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                                const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                                double *out3, double *site_lnl, void *stream) {
   if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
   if (int rc = check_sums_args(ctx, "edge_derivatives_psr", t && out3, scaler_sums, nsums); rc != PLFX_OK) return rc;
   hipStream_t s = pick(stream);
   PLFX_WS(ctx, s, w);
   // n == 0 launches too: one block, out3 = {correction, 0, 0}
-  hipError_t e = plfx::launch_edge_derivatives_psr(dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t,
-                                                   scaler_sums, nsums, w->lnl_partials, w->lnl_ticket, out3,
-                                                   site_lnl, ctx->max_blocks, s);
+  const auto launch = states == 4 ? plfx::launch_edge_derivatives_psr : plfx::launch_edge_derivatives_psr_prot;
+  hipError_t e = launch(dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums, w->lnl_partials,
+                        w->lnl_ticket, out3, site_lnl, ctx->max_blocks, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "edge_derivatives_psr launch");
   return PLFX_OK;
 }
 
-int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
-                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
-                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
-                           double *out3_host, int *evals, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                             const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                             const int32_t *wgt, double t0, double tmin, double tmax, int max_evals, double *t_opt,
+                             double *out3_host, int *evals, void *stream) {
   if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
   return edge_newton_loop(ctx, "edge_optimize_psr", t0, tmin, tmax, max_evals, t_opt, out3_host, evals, pick(stream),
                           [&](const double *d_t, double *d_out) {
-                            return plfx_edge_derivatives_psr(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt,
-                                                             d_t, nullptr, 0, d_out, nullptr, stream);
+                            return psr_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat,
+                                                        wgt, d_t, nullptr, 0, d_out, nullptr, stream);
                           });
 }
 
-
-int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges, int64_t n,
-                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
-                               const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
-                               double *t_opt, double *out3, int32_t *evals, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
+                                 int64_t n, const double *eigen, const double *rates, int ncat,
+                                 const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                 double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
+                                 void *stream) {
   if (nedges < 1 || !sumtabs)
     return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: nedges=%d / null sumtabs", nedges);
   for (int j = 0; j < nedges; j++) {
@@ -1349,31 +1349,116 @@ int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumt
   PLFX_WS(ctx, s, w);
   // groups of kMaxBatch edges, one after the other on the stream, in the
   // regions and under the ordering rule of plfx_edge_optimize_dev
+  const auto launch = states == 4 ? plfx::launch_edge_optimize_psr : plfx::launch_edge_optimize_psr_prot;
   for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
     const int c = std::min(nedges - g, plfx::kMaxBatch);
-    hipError_t e = plfx::launch_edge_optimize_psr(dtype, sumtabs + g, c, n, eigen, rates, ncat, rate_cat, wgt, t0 + g,
-                                                  tmin, tmax, max_evals, w->edge_state, w->lnl_partials, w->ws,
-                                                  t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
-                                                  evals ? evals + g : nullptr, ctx->max_blocks, s);
+    hipError_t e = launch(dtype, sumtabs + g, c, n, eigen, rates, ncat, rate_cat, wgt, t0 + g, tmin, tmax, max_evals,
+                          w->edge_state, w->lnl_partials, w->ws, t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
+                          evals ? evals + g : nullptr, ctx->max_blocks, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_psr_dev launch");
   }
   return PLFX_OK;
 }
 
-int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges, int64_t n,
-                                 const void *tipvec, void *stream) {
-  PLFX_BIND(ctx);
+static int psr_edge_sumtable_batch(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges, int nedges,
+                                   int64_t n, const void *tipvec, void *stream) {
   std::string err;
   plfx::PsrEdgeLaunchList &l = ctx->psr_edges_lowered;
-  if (plfx::lower_psr_edges(dtype, n, tipvec, edges, nedges, &l, &err) != PLFX_OK)
+  if (plfx::lower_psr_edges(dtype, n, tipvec, edges, nedges, &l, &err, states) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   hipStream_t s = pick(stream);
+  const auto launch = states == 4 ? plfx::launch_edge_sumtable_psr_batch : plfx::launch_edge_sumtable_psr_prot_batch;
   for (const plfx::PsrEdgeLaunch &it : l.items) {  // none when n == 0
-    hipError_t e = plfx::launch_edge_sumtable_psr_batch(dtype, it.tip != 0, &l.edges[it.first], it.count, n, tipvec,
-                                                        ctx->max_blocks, s);
+    hipError_t e = launch(dtype, it.tip != 0, &l.edges[it.first], it.count, n, tipvec, ctx->max_blocks, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "edge_sumtable_psr_batch launch");
   }
   return PLFX_OK;
+}
+
+int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
+                           int64_t n, const void *tipvec, void *sumtab, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_edge_sumtable(ctx, dtype, 4, tip1, x1, x2, n, tipvec, sumtab, stream);
+}
+
+int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
+                              double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_edge_derivatives(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums,
+                              out3, site_lnl, stream);
+}
+
+int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
+                           double *out3_host, int *evals, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_edge_optimize(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax, max_evals,
+                           t_opt, out3_host, evals, stream);
+}
+
+int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges, int64_t n,
+                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                               const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                               double *t_opt, double *out3, int32_t *evals, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_edge_optimize_dev(ctx, dtype, 4, sumtabs, nedges, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax,
+                               max_evals, t_opt, out3, evals, stream);
+}
+
+int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges, int64_t n,
+                                 const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  return psr_edge_sumtable_batch(ctx, dtype, 4, edges, nedges, n, tipvec, stream);
+}
+
+// ---- (11c) the branch-length half with a state count ----
+
+int plfx_edge_sumtable_psr_gen(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                               const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_edge_sumtable(ctx, dtype, states, tip1, x1, x2, n, tipvec, sumtab, stream);
+}
+
+int plfx_edge_sumtable_psr_batch_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges, int nedges,
+                                     int64_t n, const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_edge_sumtable_batch(ctx, dtype, states, edges, nedges, n, tipvec, stream);
+}
+
+int plfx_edge_derivatives_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                                  const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                                  const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                                  double *out3, double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums,
+                              out3, site_lnl, stream);
+}
+
+int plfx_edge_optimize_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                               const int32_t *wgt, double t0, double tmin, double tmax, int max_evals,
+                               double *t_opt, double *out3_host, int *evals, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_edge_optimize(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax,
+                           max_evals, t_opt, out3_host, evals, stream);
+}
+
+int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
+                                   int64_t n, const double *eigen, const double *rates, int ncat,
+                                   const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                   double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
+                                   void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  return psr_edge_optimize_dev(ctx, dtype, states, sumtabs, nedges, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin,
+                               tmax, max_evals, t_opt, out3, evals, stream);
 }
 
 // ---- (12) the PSR rate scan ----

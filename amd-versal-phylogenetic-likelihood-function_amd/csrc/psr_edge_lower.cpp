@@ -31,14 +31,15 @@ struct Span {
 }  // namespace
 
 int lower_psr_edges(int dtype, int64_t n, const void *tipvec, const plfx_psr_edge *edges, int nedges,
-                    PsrEdgeLaunchList *out, std::string *err) {
+                    PsrEdgeLaunchList *out, std::string *err, int states) {
   out->clear();
   if (dtype != PLFX_F32 && dtype != PLFX_F64) return refuse(out, err, "bad dtype");
+  if (states != 4 && states != 20) return refuse(out, err, "states not built (4, 20)");
   if (n < 0) return refuse(out, err, "n < 0");
   if (nedges < 1 || !edges) return refuse(out, err, "needs nedges >= 1 edges");
   if (n == 0) return PLFX_OK;
 
-  const size_t cb = psr_clv_bytes(dtype, n), tb = (size_t)n;
+  const size_t cb = psr_clv_bytes(dtype, n, states), tb = (size_t)n;
   for (int i = 0; i < nedges; i++) {
     const plfx_psr_edge &d = edges[i];
     if ((d.tip1 != nullptr) == (d.x1 != nullptr)) return refuse(out, err, "side 1 needs exactly one of tip / CLV", i);

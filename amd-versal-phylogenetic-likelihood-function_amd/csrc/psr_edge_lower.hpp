@@ -43,7 +43,10 @@ struct PsrEdgeLaunchList {
 // edge's table or with any edge's input -- one sort of the byte intervals and
 // one sweep.  Inputs may repeat.  Returns PLFX_OK, or PLFX_ERR_INVALID with
 // *err set and *out empty: nothing of a refused call is launched.
+// states: 4, or 20 for plfx_edge_sumtable_psr_batch_gen's protein tables -- a
+// CLV and a table are n * states values, which is what the overlap checks
+// span; any other count is refused like a bad dtype.
 int lower_psr_edges(int dtype, int64_t n, const void *tipvec, const plfx_psr_edge *edges, int nedges,
-                    PsrEdgeLaunchList *out, std::string *err);
+                    PsrEdgeLaunchList *out, std::string *err, int states = 4);
 
 }  // namespace plfx

@@ -59,6 +59,8 @@ EXPORTS = (
     "plfx_edge_optimize_psr_dev", "plfx_edge_sumtable_psr_batch",
     "plfx_site_lnl_psr", "plfx_psr_rate_scan", "plfx_psr_rate_scan_workspace", "plfx_psr_categorize",
     "plfx_plf_psr_dev_gen", "plfx_traverse_psr_gen", "plfx_root_lnl_psr_gen", "plfx_psr_site_order",
+    "plfx_edge_sumtable_psr_gen", "plfx_edge_sumtable_psr_batch_gen", "plfx_edge_derivatives_psr_gen",
+    "plfx_edge_optimize_psr_gen", "plfx_edge_optimize_psr_dev_gen",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -210,6 +212,13 @@ def load():
                                         i32, vp, i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
     L.plfx_root_lnl_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
     L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
+    L.plfx_edge_sumtable_psr_gen.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, vp, vp]
+    L.plfx_edge_sumtable_psr_batch_gen.argtypes = [vp, i32, i32, C.POINTER(PsrEdge), i32, i64, vp, vp]
+    L.plfx_edge_derivatives_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.plfx_edge_optimize_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32, dp, dp,
+                                             C.POINTER(i32), vp]
+    L.plfx_edge_optimize_psr_dev_gen.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl,
+                                                 dbl, i32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -895,6 +904,96 @@ class Context:
         self._check(self._L.plfx_root_lnl_psr_gen(
             self.h, F32 if x.dtype == torch.float32 else F64, S, p(x), int(n), p(freq), p(wgt), p(scaler_sums),
             0 if scaler_sums is None else scaler_sums.numel(), p(out), p(site_lnl), self._sh(stream)))
+
+    # -- (11c) the branch-length half with a state count ---------------------
+    def edge_sumtable_psr_gen(self, states, x2, sumtab, n, x1=None, tip1=None, tipvec=None, stream=None):
+        """edge_sumtable_psr() with a state count (plfx.h section 11c): states
+        4 is edge_sumtable_psr() itself; with states 20 the CLVs and the table
+        hold 20*n values and tip1 holds protein codes (row min(code, 23) of the
+        PROT_CODES x 20 eigen-convention tipvec)."""
+        import torch
+
+        S = self._psr_gen_states(states)
+        dt = sumtab.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
+            _tensor(t, k, dt, S * n, optional=True)
+        _tensor(tip1, "tip1", torch.uint8, n, optional=True)
+        p = _ptr
+        self._check(self._L.plfx_edge_sumtable_psr_gen(
+            self.h, F32 if dt == torch.float32 else F64, S, p(tip1), p(x1), p(x2), int(n),
+            self._tipvec(tipvec, dt, S), p(sumtab), self._sh(stream)))
+
+    def edge_sumtables_psr_gen(self, states, edges, n, tipvec=None, stream=None):
+        """edge_sumtables_psr() with a state count (plfx_edge_sumtable_psr_batch_gen):
+        every CLV and table holds states*n values."""
+        import torch
+
+        S = self._psr_gen_states(states)
+        if isinstance(edges, dict):
+            edges = [edges]
+        n = int(n)
+        dt = edges[0]["sumtab"].dtype if edges and edges[0].get("sumtab") is not None else torch.float64
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        arr = (PsrEdge * max(1, len(edges)))()
+        for i, e in enumerate(edges):
+            for k in ("x1", "x2", "sumtab"):
+                _tensor(e.get(k), k, dt, S * n, optional=True)
+            _tensor(e.get("tip1"), "tip1", torch.uint8, n, optional=True)
+            arr[i] = PsrEdge(*(_ptr(e.get(k)) for k in ("tip1", "x1", "x2", "sumtab")))
+        self._check(self._L.plfx_edge_sumtable_psr_batch_gen(
+            self.h, F32 if dt == torch.float32 else F64, S, arr, len(edges), n, self._tipvec(tipvec, dt, S),
+            self._sh(stream)))
+
+    def _edge_args_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, wgt):
+        """(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt) of the section-11c calls."""
+        S = self._psr_gen_states(states)
+        a = self._edge_args(sumtab, n, eigen, rates, None, wgt, S, rate_cat, psr=True)
+        return a[:2] + (S,) + a[2:]
+
+    def edge_derivatives_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None,
+                                 scaler_sums=None, site_lnl=None, stream=None):
+        """edge_derivatives_psr() with a state count (plfx.h section 11c): with
+        states 20 the table holds 20*n values and eigen is what
+        pmatrix(states=20) takes."""
+        args = self._edge_args_psr_gen(states, sumtab, n, eigen, rates, rate_cat, wgt)
+        self._edge_derivatives(self._L.plfx_edge_derivatives_psr_gen, args, n, t, out, scaler_sums, site_lnl, stream)
+
+    def optimize_branch_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0,
+                                max_evals=64, wgt=None, stream=None):
+        """optimize_branch_psr() with a state count (plfx_edge_optimize_psr_gen,
+        host-synchronous).  Returns (t, lnL, d1, d2, evals)."""
+        args = self._edge_args_psr_gen(states, sumtab, n, eigen, rates, rate_cat, wgt)
+        t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
+        self._check(self._L.plfx_edge_optimize_psr_gen(*args, float(t0), float(tmin), float(tmax), int(max_evals),
+                                                       C.byref(t), out, C.byref(ev), self._sh(stream)))
+        return t.value, out[0], out[1], out[2], ev.value
+
+    def optimize_branches_psr_gen(self, states, sumtabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=1e-8,
+                                  tmax=10.0, max_evals=64, out3=None, evals=None, wgt=None, stream=None):
+        """optimize_branches_psr() with a state count (plfx_edge_optimize_psr_dev_gen):
+        asynchronous, capture-safe; sumtabs: device tensors of states*n values each."""
+        import torch
+
+        m = len(sumtabs)
+        if m < 1:
+            raise PlfxError(ERR_INVALID, "sumtabs must hold at least one sum table")
+        for st in sumtabs:
+            if st.dtype != sumtabs[0].dtype:
+                raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
+            args = self._edge_args_psr_gen(states, st, n, eigen, rates, rate_cat, wgt)
+        for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
+                              ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
+            _tensor(x, k, dt, cnt, optional=True)
+        if t0 is None or t_opt is None:
+            raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
+        p = _ptr
+        tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
+        self._check(self._L.plfx_edge_optimize_psr_dev_gen(*args[:3], tabs, m, *args[4:], p(t0), float(tmin),
+                                                           float(tmax), int(max_evals), p(t_opt), p(out3), p(evals),
+                                                           self._sh(stream)))
 
     def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
         """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the

@@ -781,8 +781,8 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
  * argument, as plfx_plf_dev_gen stands beside plfx_plf_dev_f64: states == 4 is
  * section (11) itself (the same kernels, the same bits), states == 20 is the
  * protein path described here, any other value PLFX_ERR_UNSUPPORTED.  The
- * branch-length half (the protein versions of plfx_edge_*_psr and of section
- * 12's rate scan) does not exist yet.
+ * branch-length half (the protein versions of plfx_edge_*_psr) is section
+ * (11c); the protein version of section 12's rate scan does not exist yet.
  * With 20 states a PSR CLV is x[site*20 + state] -- n * 20 values of dtype
  * (f32 or f64), a quarter of the Gamma protein layout, base 16-byte aligned;
  *   left, right: ncat * 400 values [c][k][l] -- what plfx_pmatrix(states = 20)
@@ -849,6 +849,75 @@ int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, i
  * arrays of n entries.  PLFX_ERR_INVALID for a NULL pointer, n < 0 or ncat
  * outside 1..PLFX_PSR_MAX_CATS; n == 0 writes nothing. */
 int plfx_psr_site_order(const uint8_t *rate_cat, int64_t n, int ncat, int64_t *perm);
+
+/* ---- (11c) per-site rate categories for protein: the branch-length half ----
+ * (PROTCAT: the sum table, one and batched, the edge derivatives and the two
+ * Newton loops; extension).  The five entry points below are their
+ * section-(11) namesakes with a `states` argument after dtype, as section
+ * (11b)'s are: states == 4 is section (11) itself (the same launchers, the
+ * same bits), states == 20 the protein path described here, any other value
+ * PLFX_ERR_UNSUPPORTED.  The CLVs must be in the eigen convention, as in
+ * section (10).  With 20 states a sum table is n * 20 values of dtype, 16-byte
+ * aligned; tipvec is the 24 x 20 table of dtype a coded side indexes by
+ * min(code, 23); eigen is what plfx_pmatrix(states = 20) takes, of which only
+ * lambda[0..19] is read; rates, rate_cat, the clamp c_i = min(rate_cat[i],
+ * ncat-1) and 1 <= ncat <= PLFX_PSR_MAX_CATS as in section (11).
+ *
+ * SITE ORDER.  Unlike the node of section (11b), the edge kernels make no pass
+ * per category: a lane owns a site and reads its category's 60 factors from a
+ * table in the block's local memory, whose rows are padded so that lanes in
+ * different categories read different banks.  Every site's terms are the same
+ * bits for any order of the sites, and so is the time: measured at 2^14, 2^18
+ * and 2^20 f64 sites with 25 categories, uniformly random categories and
+ * shuffled whole runs of 64 sites both take 0.98 to 1.00 of the sorted time
+ * (DESIGN.md section 4).  Sorting the sites, which the node needs, does not
+ * matter to the calls of this section. */
+
+/* plfx_edge_sumtable_psr with a state count: sumtab[i][k] = x1[i][k] *
+ * x2[i][k], one multiply rounded in dtype, n * states values.  Side 1 is dense
+ * or coded; with states == 20 a coded side reads row min(code, 23) of the 24 x
+ * 20 tipvec, which is required with tip1.  The 16-byte alignment and overlap
+ * rules are plfx_edge_sumtable_psr's, the overlap check over n * states
+ * values. */
+int plfx_edge_sumtable_psr_gen(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                               const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream);
+
+/* plfx_edge_sumtable_psr_batch with a state count: the same plfx_psr_edge
+ * array, dense-side edges first, then coded ones, in launches of up to 32 with
+ * edge = blockIdx.y; each table is exactly what the one-edge call writes.
+ * Every check runs before the first launch; the byte-overlap sweep across the
+ * edges spans n * states values per CLV and table. */
+int plfx_edge_sumtable_psr_batch_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges,
+                                     int nedges, int64_t n, const void *tipvec, void *stream);
+
+/* plfx_edge_derivatives_psr with a state count: out3 as there, in f64, with
+ * x_k = lambda_k * rates[c_i], e = exp(x_k t), and L, L1, L2 = sum_k
+ * sumtab[i][k] * {e, e x, e x x} over k = 0..states-1, from +0.0, ascending k.
+ * site_lnl, wgt, scaler_sums and n == 0 (out3 = {correction, 0, 0}) as in
+ * section (11); the fixed-order reduction: deterministic, asynchronous,
+ * capture-safe. */
+int plfx_edge_derivatives_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                                  const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                                  const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
+                                  double *out3, double *site_lnl, void *stream);
+
+/* plfx_edge_optimize_psr over plfx_edge_derivatives_psr_gen: host-synchronous,
+ * refuses a capturing stream. */
+int plfx_edge_optimize_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
+                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                               const int32_t *wgt, double t0, double tmin, double tmax, int max_evals,
+                               double *t_opt, double *out3_host, int *evals, void *stream);
+
+/* plfx_edge_optimize_psr_dev with a state count: the same contract -- exactly
+ * max_evals launches per group of up to 32 edges, the same workspace regions,
+ * at most 4096 / count blocks per edge of a group; a one-edge call has
+ * plfx_edge_derivatives_psr_gen's grid, slots and summation order, so its
+ * t_opt, out3 and evals are plfx_edge_optimize_psr_gen's bit for bit. */
+int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
+                                   int64_t n, const double *eigen, const double *rates, int ncat,
+                                   const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
+                                   double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
+                                   void *stream);
 
 /* ---- (12) the PSR rate scan and rate categorisation (extension) -----------
  * Section (11) takes rate_cat and the category rates as inputs; this section
