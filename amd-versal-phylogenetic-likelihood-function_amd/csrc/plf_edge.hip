@@ -48,10 +48,10 @@ int64_t edge_deriv_grid(int states, int64_t n, int max_blocks) {
     auto kernel = &dev::edge_deriv_kernel<T, 4, 4>;
     int64_t gx = grid_x((const void *)kernel, cache4, n, kWavesPerBlock * 64, 1, max_blocks);
     if (max_blocks <= 0) gx = std::min<int64_t>(gx, 2 * (int64_t)cu_count());
-    return std::min<int64_t>(gx, kLnlMaxGrid);
+    return lnl_cap(gx);
   }
   auto kernel = &dev::edge_deriv_prot_kernel<T>;
-  return std::min<int64_t>(grid_x((const void *)kernel, cache20, n, 64, 1, max_blocks), kLnlMaxGrid);
+  return lnl_cap(grid_x((const void *)kernel, cache20, n, 64, 1, max_blocks));
 }
 
 template <typename T>
@@ -67,10 +67,7 @@ hipError_t launch_edge_deriv_t(int states, const T *st, int64_t n, const double 
                 t, sums, nsums, partials, ticket, out, site_lnl);
 }
 
-// The device loop: max_evals launches of edge_opt_kernel over the group's
-// edges (blockIdx.y); the first of them initialises the per-edge state.  The
-// per-edge grid is the one-edge grid unless the group's 3 * gx * count slots
-// would not fit the 3 * kLnlMaxGrid doubles of `partials`.
+// The device loop (edge_opt_loop) of edge_opt_kernel.
 template <typename T, int S>
 hipError_t launch_edge_opt_t(const void *const *tabs, int count, int64_t n, const double *lambda,
                              const double *rates, const double *catw, const int32_t *wgt, const double *t0,
@@ -78,16 +75,12 @@ hipError_t launch_edge_opt_t(const void *const *tabs, int count, int64_t n, cons
                              unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
                              int max_blocks, hipStream_t s) {
   static_assert(dev::kMaxBatch == kMaxBatch && dev::kWsWords == kWsWords, "batch constants");
-  dev::EdgeOptTabs a{};
-  for (int j = 0; j < count; j++) a.st[j] = tabs[j];
-  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(edge_deriv_grid<T>(S, n, max_blocks), kLnlMaxGrid / count));
-  for (int i = 0; i < max_evals; i++) {
-    hipError_t e = launch(&dev::edge_opt_kernel<T, S>, dim3((unsigned)gx, (unsigned)count), kBlock, s, a, n, lambda,
-                          rates, catw, wgt, t0, tmin, tmax, max_evals, (int)(i == 0),
-                          static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3, evals);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return edge_opt_loop<dev::EdgeOptTabs>(
+      tabs, count, max_evals, edge_deriv_grid<T>(S, n, max_blocks),
+      [&](dim3 grid, const dev::EdgeOptTabs &a, int first) {
+        return launch(&dev::edge_opt_kernel<T, S>, grid, kBlock, s, a, n, lambda, rates, catw, wgt, t0, tmin, tmax,
+                      max_evals, first, static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3, evals);
+      });
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-// plf_launch.hpp -- host-side helpers shared by the launchers of the three HIP
+// plf_launch.hpp -- host-side helpers shared by the launchers of the six HIP
 // translation units (plf_kernels.hip, plf_prot_valu.hip,
-// plf_prot_valu_exact.hip): pick a grid, pick a kernel instantiation, launch.
+// plf_prot_valu_exact.hip, plf_edge.hip, plf_psr.hip, plf_psr_prot.hip): pick
+// a grid, pick a kernel instantiation, launch.
 // Internal to libplfx; no device code.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,10 +57,31 @@ inline int64_t grid_x(const void *kernel, int &cache, int64_t n, int sites_per_b
   return blocks < 1 ? 1 : blocks;
 }
 
+// the grid of a kernel whose blocks each own a slot of the kLnlMaxGrid partial sums
+inline int64_t lnl_cap(int64_t gx) { return std::min<int64_t>(gx, kLnlMaxGrid); }
+
 template <typename K, typename... A>
 hipError_t launch(K kernel, dim3 grid, int threads, hipStream_t s, const A &...args) {
   hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, args...);
   return hipGetLastError();
+}
+
+// The branch-length loop on the device: max_evals launches over the group's
+// `count` edges (blockIdx.y), the first of which initialises the per-edge
+// state.  Tabs: the device's struct of the tables' pointers (no device header
+// here); eval(grid, tabs, first) enqueues one launch of the caller's kernel.
+// The per-edge grid is the one-edge grid gx1 unless the group's 3 * gx * count
+// slots would not fit the 3 * kLnlMaxGrid doubles of the partials.
+template <typename Tabs, typename Eval>
+hipError_t edge_opt_loop(const void *const *tabs, int count, int max_evals, int64_t gx1, Eval eval) {
+  Tabs a{};
+  for (int j = 0; j < count; j++) a.st[j] = tabs[j];
+  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(gx1, kLnlMaxGrid / count));
+  for (int i = 0; i < max_evals; i++) {
+    hipError_t e = eval(dim3((unsigned)gx, (unsigned)count), a, (int)(i == 0));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // A node kernel over gx blocks: DnaArgs as the kernel's argument list, the

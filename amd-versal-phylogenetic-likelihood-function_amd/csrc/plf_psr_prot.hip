@@ -52,8 +52,7 @@ hipError_t launch_plf_psr_prot_t(const NodeDescH *nodes, int count, const void *
 template <typename T>
 int64_t edge_deriv_psr_prot_grid(int64_t n, int max_blocks) {
   static int cache = 0;
-  return std::min<int64_t>(
-      grid_x((const void *)&dev::edge_deriv_psr_prot_kernel<T>, cache, n, kBlock, 1, max_blocks), kLnlMaxGrid);
+  return lnl_cap(grid_x((const void *)&dev::edge_deriv_psr_prot_kernel<T>, cache, n, kBlock, 1, max_blocks));
 }
 
 // 16-B chunks of a table of n sites, and those a block of the sum-table kernels covers per trip
@@ -87,8 +86,7 @@ hipError_t launch_root_lnl_psr_prot(int dtype, const void *x, int64_t n, const d
         using T = real_t<k64()>;
         static int cache = 0;
         auto kernel = &dev::root_lnl_psr_prot_kernel<T>;
-        const int64_t gx =
-            std::min<int64_t>(grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks), kLnlMaxGrid);
+        const int64_t gx = lnl_cap(grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks));
         return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, freq, wgt, scaler_sums, nsums,
                       partials, ticket, out, site_lnl);
       },
@@ -142,11 +140,7 @@ hipError_t launch_edge_derivatives_psr_prot(int dtype, const void *sumtab, int64
       bools{dtype == 1});
 }
 
-// The device loop (plf_psr.hip launch_edge_optimize_psr for tables of 20
-// states): max_evals launches of edge_opt_psr_prot_kernel over the group's
-// edges (blockIdx.y); the first of them initialises the per-edge state.  The
-// per-edge grid is the one-edge grid unless the group's 3 * gx * count slots
-// would not fit the 3 * kLnlMaxGrid doubles of `partials`.
+// The device loop (edge_opt_loop) of edge_opt_psr_prot_kernel.
 hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, int count, int64_t n,
                                          const double *lambda, const double *rates, int ncat,
                                          const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
@@ -157,17 +151,13 @@ hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, 
   return dispatch(
       [&](auto k64) {
         using T = real_t<k64()>;
-        dev::EdgeOptTabs a{};
-        for (int j = 0; j < count; j++) a.st[j] = sumtabs[j];
-        const int64_t gx = std::max<int64_t>(
-            1, std::min<int64_t>(edge_deriv_psr_prot_grid<T>(n, max_blocks), kLnlMaxGrid / count));
-        for (int i = 0; i < max_evals; i++) {
-          hipError_t e = launch(&dev::edge_opt_psr_prot_kernel<T>, dim3((unsigned)gx, (unsigned)count), kBlock, s, a,
-                                n, lambda, rates, ncat, rate_cat, wgt, t0, tmin, tmax, max_evals, (int)(i == 0),
-                                static_cast<EdgeNewtonStep *>(state), partials, ws, t_opt, out3, evals);
-          if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+        return edge_opt_loop<dev::EdgeOptTabs>(
+            sumtabs, count, max_evals, edge_deriv_psr_prot_grid<T>(n, max_blocks),
+            [&](dim3 grid, const dev::EdgeOptTabs &a, int first) {
+              return launch(&dev::edge_opt_psr_prot_kernel<T>, grid, kBlock, s, a, n, lambda, rates, ncat, rate_cat,
+                            wgt, t0, tmin, tmax, max_evals, first, static_cast<EdgeNewtonStep *>(state), partials, ws,
+                            t_opt, out3, evals);
+            });
       },
       bools{dtype == 1});
 }

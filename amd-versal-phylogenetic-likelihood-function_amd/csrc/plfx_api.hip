@@ -670,6 +670,42 @@ int edge_newton_loop(plfx_ctx *ctx, const char *who, double t0, double tmin, dou
   return PLFX_OK;
 }
 
+// The device-resident Newton of plfx_edge_optimize_dev and
+// plfx_edge_optimize_psr_dev_gen (`who`): check_table(sumtab) checks one table
+// with the call's model arguments, launch(g, c, w, s) enqueues the c edges
+// from edge g on stream s with the stream's workspace w.
+template <typename Check, typename Launch>
+int edge_optimize_dev(plfx_ctx *ctx, const char *who, const void *const *sumtabs, int nedges, const double *t0,
+                      double tmin, double tmax, int max_evals, double *t_opt, void *stream, Check check_table,
+                      Launch launch) {
+  if (nedges < 1 || !sumtabs) return fail(ctx, PLFX_ERR_INVALID, "%s: nedges=%d / null sumtabs", who, nedges);
+  for (int j = 0; j < nedges; j++) {
+    if (!sumtabs[j]) return fail(ctx, PLFX_ERR_INVALID, "%s: sum table %d is null", who, j);
+    if (int rc = check_table(sumtabs[j]); rc != PLFX_OK) return rc;
+  }
+  if (!t0 || !t_opt) return fail(ctx, PLFX_ERR_INVALID, "%s: null t0 / t_opt", who);
+  if (!(tmin > 0.0 && tmin <= tmax && std::isfinite(tmax)) || max_evals < 1 || max_evals > PLFX_EDGE_MAX_EVALS)
+    return fail(ctx, PLFX_ERR_INVALID, "%s: needs 0 < tmin <= tmax < inf and 1 <= max_evals <= %d", who,
+                PLFX_EDGE_MAX_EVALS);
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // groups of kMaxBatch edges, one after the other on the stream: a group's
+  // launches are done with the state, ticket and partial regions before the
+  // next group's first launch rewrites the state
+  for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
+    hipError_t e = launch(g, std::min(nedges - g, plfx::kMaxBatch), w, s);
+    if (e != hipSuccess) return hip_fail(ctx, e, (std::string(who) + " launch").c_str());
+  }
+  return PLFX_OK;
+}
+
+// the state counts the per-site-rate entry points are built for
+int check_psr_states(plfx_ctx *ctx, int states) {
+  if (states != 4 && states != 20)
+    return fail(ctx, PLFX_ERR_UNSUPPORTED, "per-site rate categories: states=%d not built (4, 20)", states);
+  return PLFX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1138,37 +1174,83 @@ int plfx_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *con
                            const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
                            double *t_opt, double *out3, int32_t *evals, void *stream) {
   PLFX_BIND(ctx);
-  if (nedges < 1 || !sumtabs) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: nedges=%d / null sumtabs", nedges);
-  for (int j = 0; j < nedges; j++) {
-    if (!sumtabs[j]) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: sum table %d is null", j);
-    if (int rc = check_edge_args(ctx, dtype, states, sumtabs[j], n, eigen, rates, ncat); rc != PLFX_OK) return rc;
-  }
-  if (!t0 || !t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: null t0 / t_opt");
-  if (!(tmin > 0.0 && tmin <= tmax && std::isfinite(tmax)) || max_evals < 1 || max_evals > PLFX_EDGE_MAX_EVALS)
-    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_dev: needs 0 < tmin <= tmax < inf and 1 <= max_evals <= %d",
-                PLFX_EDGE_MAX_EVALS);
-  hipStream_t s = pick(stream);
-  PLFX_WS(ctx, s, w);
-  // groups of kMaxBatch edges, one after the other on the stream: a group's
-  // launches are done with the state, ticket and partial regions before the
-  // next group's first launch rewrites the state
-  for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
-    const int c = std::min(nedges - g, plfx::kMaxBatch);
-    hipError_t e = plfx::launch_edge_optimize(dtype, states, sumtabs + g, c, n, eigen, rates, catw, wgt, t0 + g, tmin,
-                                              tmax, max_evals, w->edge_state, w->lnl_partials, w->ws, t_opt + g,
-                                              out3 ? out3 + 3 * (size_t)g : nullptr, evals ? evals + g : nullptr,
-                                              ctx->max_blocks, s);
-    if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_dev launch");
-  }
-  return PLFX_OK;
+  return edge_optimize_dev(
+      ctx, "edge_optimize_dev", sumtabs, nedges, t0, tmin, tmax, max_evals, t_opt, stream,
+      [&](const void *st) { return check_edge_args(ctx, dtype, states, st, n, eigen, rates, ncat); },
+      [&](int g, int c, StreamWs *w, hipStream_t s) {
+        return plfx::launch_edge_optimize(dtype, states, sumtabs + g, c, n, eigen, rates, catw, wgt, t0 + g, tmin, tmax,
+                                          max_evals, w->edge_state, w->lnl_partials, w->ws, t_opt + g,
+                                          out3 ? out3 + 3 * (size_t)g : nullptr, evals ? evals + g : nullptr,
+                                          ctx->max_blocks, s);
+      });
 }
 
-// ---- (11) per-site rate categories ----
+// ---- (11) per-site rate categories; (11b), (11c) the same with a state count ----
 
-// The three entry points for `states` 4 (this section) and 20 (section 11b).
-static int psr_nodes(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count, const void *EV,
+// Each entry point of section 11 is its _gen twin with 4 states.  The _gen
+// entry points: states 4 runs plf_psr.hip's launchers, states 20
+// plf_psr_prot.hip's; the checks, the host loop and the workspace regions are
+// shared.
+
+int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
                      int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
                      void *stream) {
+  return plfx_plf_psr_dev_gen(ctx, dtype, 4, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
+}
+
+int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
+                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
+  return plfx_traverse_psr_gen(ctx, dtype, 4, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat, ncat, wgt,
+                               scalers, scaler_sums, tipvec, stream);
+}
+
+int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
+                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                      double *site_lnl, void *stream) {
+  return plfx_root_lnl_psr_gen(ctx, dtype, 4, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
+}
+
+int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
+                           int64_t n, const void *tipvec, void *sumtab, void *stream) {
+  return plfx_edge_sumtable_psr_gen(ctx, dtype, 4, tip1, x1, x2, n, tipvec, sumtab, stream);
+}
+
+int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
+                              double *site_lnl, void *stream) {
+  return plfx_edge_derivatives_psr_gen(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums,
+                                       nsums, out3, site_lnl, stream);
+}
+
+int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
+                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
+                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
+                           double *out3_host, int *evals, void *stream) {
+  return plfx_edge_optimize_psr_gen(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax,
+                                    max_evals, t_opt, out3_host, evals, stream);
+}
+
+int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges, int64_t n,
+                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
+                               const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
+                               double *t_opt, double *out3, int32_t *evals, void *stream) {
+  return plfx_edge_optimize_psr_dev_gen(ctx, dtype, 4, sumtabs, nedges, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin,
+                                        tmax, max_evals, t_opt, out3, evals, stream);
+}
+
+int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges, int64_t n,
+                                 const void *tipvec, void *stream) {
+  return plfx_edge_sumtable_psr_batch_gen(ctx, dtype, 4, edges, nedges, n, tipvec, stream);
+}
+
+int plfx_plf_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count,
+                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                         const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
   static_assert(PLFX_PSR_MAX_CATS <= 256, "a category is one byte");
   std::string err;
   const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states};
@@ -1180,10 +1262,13 @@ static int psr_nodes(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *
   return execute_psr(ctx, ctx->psr_lowered, call, wgt, tipvec, s, w->ws);
 }
 
-static int psr_traverse(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops, void *const *clv,
-                        const uint8_t *const *tips, int nslots, const void *pmats, int npmats, const void *EV,
-                        int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, uint8_t *const *scalers,
-                        int64_t *scaler_sums, const void *tipvec, void *stream) {
+int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
+                          void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
+                          int npmats, const void *EV, int64_t n, const uint8_t *rate_cat, int ncat,
+                          const int32_t *wgt, uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
+                          void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
   for (int &c : ctx->sched) c = 0;
   if (nops < 0 || (nops > 0 && (!ops || !clv))) return fail(ctx, PLFX_ERR_INVALID, "bad traverse_psr arguments");
   // level pairs alone: the deeper passes of entries 0..3 of the schedule are not built for PSR;
@@ -1208,9 +1293,11 @@ static int psr_traverse(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op
   return publish_sched(ctx, plan, ctx->psr_lowered.launches());
 }
 
-static int psr_root_lnl(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
-                        const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
-                        double *site_lnl, void *stream) {
+int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                          const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
+                          double *site_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   if (int rc = check_sums_args(ctx, "root_lnl_psr", out_lnl && n >= 0 && (n == 0 || x), scaler_sums, nsums);
       rc != PLFX_OK)
@@ -1229,69 +1316,10 @@ static int psr_root_lnl(plfx_ctx *ctx, int dtype, int states, const void *x, int
   return PLFX_OK;
 }
 
-int plfx_plf_psr_dev(plfx_ctx *ctx, int dtype, const plfx_psr_node *nodes, int count, const void *EV,
-                     int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt, const void *tipvec,
-                     void *stream) {
-  PLFX_BIND(ctx);
-  return psr_nodes(ctx, dtype, 4, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
-}
-
-int plfx_traverse_psr(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, void *const *clv,
-                      const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
-                      const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
-                      uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_traverse(ctx, dtype, 4, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat, ncat, wgt,
-                      scalers, scaler_sums, tipvec, stream);
-}
-
-int plfx_root_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
-                      const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
-                      double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_root_lnl(ctx, dtype, 4, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
-}
-
-// ---- (11b) the same with a state count: 4 is section 11, 20 the protein kernels ----
-
-static int check_psr_states(plfx_ctx *ctx, int states) {
-  if (states != 4 && states != 20)
-    return fail(ctx, PLFX_ERR_UNSUPPORTED, "per-site rate categories: states=%d not built (4, 20)", states);
-  return PLFX_OK;
-}
-
-int plfx_plf_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count,
-                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
-                         const void *tipvec, void *stream) {
+int plfx_edge_sumtable_psr_gen(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
+                               const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_nodes(ctx, dtype, states, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
-}
-
-int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
-                          void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
-                          int npmats, const void *EV, int64_t n, const uint8_t *rate_cat, int ncat,
-                          const int32_t *wgt, uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
-                          void *stream) {
-  PLFX_BIND(ctx);
-  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_traverse(ctx, dtype, states, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat, ncat, wgt,
-                      scalers, scaler_sums, tipvec, stream);
-}
-
-int plfx_root_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
-                          const int32_t *wgt, const int64_t *scaler_sums, int nsums, double *out_lnl,
-                          double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
-  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_root_lnl(ctx, dtype, states, x, n, freq, wgt, scaler_sums, nsums, out_lnl, site_lnl, stream);
-}
-
-// The branch-length half of sections (11) and (11c): states 4 runs plf_psr.hip's
-// launchers, states 20 plf_psr_prot.hip's; the checks, the host loop and the
-// workspace regions are shared.  The callers have bound the context.
-static int psr_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
-                             const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
   if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
   const int rc = check_sumtable_args(ctx, tip1, x1, x2, n, tipvec, sumtab, plfx::psr_clv_bytes(dtype, n, states));
   if (rc != PLFX_OK || n == 0) return rc;
@@ -1302,66 +1330,10 @@ static int psr_edge_sumtable(plfx_ctx *ctx, int dtype, int states, const uint8_t
   return PLFX_OK;
 }
 
-static int psr_edge_derivatives(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
-                                const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
-                                const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
-                                double *out3, double *site_lnl, void *stream) {
-  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
-  if (int rc = check_sums_args(ctx, "edge_derivatives_psr", t && out3, scaler_sums, nsums); rc != PLFX_OK) return rc;
-  hipStream_t s = pick(stream);
-  PLFX_WS(ctx, s, w);
-  // n == 0 launches too: one block, out3 = {correction, 0, 0}
-  const auto launch = states == 4 ? plfx::launch_edge_derivatives_psr : plfx::launch_edge_derivatives_psr_prot;
-  hipError_t e = launch(dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums, w->lnl_partials,
-                        w->lnl_ticket, out3, site_lnl, ctx->max_blocks, s);
-  if (e != hipSuccess) return hip_fail(ctx, e, "edge_derivatives_psr launch");
-  return PLFX_OK;
-}
-
-static int psr_edge_optimize(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
-                             const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
-                             const int32_t *wgt, double t0, double tmin, double tmax, int max_evals, double *t_opt,
-                             double *out3_host, int *evals, void *stream) {
-  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
-  return edge_newton_loop(ctx, "edge_optimize_psr", t0, tmin, tmax, max_evals, t_opt, out3_host, evals, pick(stream),
-                          [&](const double *d_t, double *d_out) {
-                            return psr_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat,
-                                                        wgt, d_t, nullptr, 0, d_out, nullptr, stream);
-                          });
-}
-
-static int psr_edge_optimize_dev(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
-                                 int64_t n, const double *eigen, const double *rates, int ncat,
-                                 const uint8_t *rate_cat, const int32_t *wgt, const double *t0, double tmin,
-                                 double tmax, int max_evals, double *t_opt, double *out3, int32_t *evals,
-                                 void *stream) {
-  if (nedges < 1 || !sumtabs)
-    return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: nedges=%d / null sumtabs", nedges);
-  for (int j = 0; j < nedges; j++) {
-    if (!sumtabs[j]) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: sum table %d is null", j);
-    if (int rc = check_psr_edge_args(ctx, dtype, sumtabs[j], n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
-  }
-  if (!t0 || !t_opt) return fail(ctx, PLFX_ERR_INVALID, "edge_optimize_psr_dev: null t0 / t_opt");
-  if (!(tmin > 0.0 && tmin <= tmax && std::isfinite(tmax)) || max_evals < 1 || max_evals > PLFX_EDGE_MAX_EVALS)
-    return fail(ctx, PLFX_ERR_INVALID,
-                "edge_optimize_psr_dev: needs 0 < tmin <= tmax < inf and 1 <= max_evals <= %d", PLFX_EDGE_MAX_EVALS);
-  hipStream_t s = pick(stream);
-  PLFX_WS(ctx, s, w);
-  // groups of kMaxBatch edges, one after the other on the stream, in the
-  // regions and under the ordering rule of plfx_edge_optimize_dev
-  const auto launch = states == 4 ? plfx::launch_edge_optimize_psr : plfx::launch_edge_optimize_psr_prot;
-  for (int g = 0; g < nedges; g += plfx::kMaxBatch) {
-    const int c = std::min(nedges - g, plfx::kMaxBatch);
-    hipError_t e = launch(dtype, sumtabs + g, c, n, eigen, rates, ncat, rate_cat, wgt, t0 + g, tmin, tmax, max_evals,
-                          w->edge_state, w->lnl_partials, w->ws, t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
-                          evals ? evals + g : nullptr, ctx->max_blocks, s);
-    if (e != hipSuccess) return hip_fail(ctx, e, "edge_optimize_psr_dev launch");
-  }
-  return PLFX_OK;
-}
-
-static int psr_edge_sumtable_batch(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges, int nedges,
-                                   int64_t n, const void *tipvec, void *stream) {
+int plfx_edge_sumtable_psr_batch_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges, int nedges,
+                                     int64_t n, const void *tipvec, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
   std::string err;
   plfx::PsrEdgeLaunchList &l = ctx->psr_edges_lowered;
   if (plfx::lower_psr_edges(dtype, n, tipvec, edges, nedges, &l, &err, states) != PLFX_OK)
@@ -1375,69 +1347,22 @@ static int psr_edge_sumtable_batch(plfx_ctx *ctx, int dtype, int states, const p
   return PLFX_OK;
 }
 
-int plfx_edge_sumtable_psr(plfx_ctx *ctx, int dtype, const uint8_t *tip1, const void *x1, const void *x2,
-                           int64_t n, const void *tipvec, void *sumtab, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_edge_sumtable(ctx, dtype, 4, tip1, x1, x2, n, tipvec, sumtab, stream);
-}
-
-int plfx_edge_derivatives_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
-                              const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
-                              const double *t, const int64_t *scaler_sums, int nsums, double *out3,
-                              double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_edge_derivatives(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums,
-                              out3, site_lnl, stream);
-}
-
-int plfx_edge_optimize_psr(plfx_ctx *ctx, int dtype, const void *sumtab, int64_t n, const double *eigen,
-                           const double *rates, int ncat, const uint8_t *rate_cat, const int32_t *wgt,
-                           double t0, double tmin, double tmax, int max_evals, double *t_opt,
-                           double *out3_host, int *evals, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_edge_optimize(ctx, dtype, 4, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax, max_evals,
-                           t_opt, out3_host, evals, stream);
-}
-
-int plfx_edge_optimize_psr_dev(plfx_ctx *ctx, int dtype, const void *const *sumtabs, int nedges, int64_t n,
-                               const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
-                               const int32_t *wgt, const double *t0, double tmin, double tmax, int max_evals,
-                               double *t_opt, double *out3, int32_t *evals, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_edge_optimize_dev(ctx, dtype, 4, sumtabs, nedges, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax,
-                               max_evals, t_opt, out3, evals, stream);
-}
-
-int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *edges, int nedges, int64_t n,
-                                 const void *tipvec, void *stream) {
-  PLFX_BIND(ctx);
-  return psr_edge_sumtable_batch(ctx, dtype, 4, edges, nedges, n, tipvec, stream);
-}
-
-// ---- (11c) the branch-length half with a state count ----
-
-int plfx_edge_sumtable_psr_gen(plfx_ctx *ctx, int dtype, int states, const uint8_t *tip1, const void *x1,
-                               const void *x2, int64_t n, const void *tipvec, void *sumtab, void *stream) {
-  PLFX_BIND(ctx);
-  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_edge_sumtable(ctx, dtype, states, tip1, x1, x2, n, tipvec, sumtab, stream);
-}
-
-int plfx_edge_sumtable_psr_batch_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_edge *edges, int nedges,
-                                     int64_t n, const void *tipvec, void *stream) {
-  PLFX_BIND(ctx);
-  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_edge_sumtable_batch(ctx, dtype, states, edges, nedges, n, tipvec, stream);
-}
-
 int plfx_edge_derivatives_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
                                   const double *eigen, const double *rates, int ncat, const uint8_t *rate_cat,
                                   const int32_t *wgt, const double *t, const int64_t *scaler_sums, int nsums,
                                   double *out3, double *site_lnl, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_edge_derivatives(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums,
-                              out3, site_lnl, stream);
+  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
+  if (int rc = check_sums_args(ctx, "edge_derivatives_psr", t && out3, scaler_sums, nsums); rc != PLFX_OK) return rc;
+  hipStream_t s = pick(stream);
+  PLFX_WS(ctx, s, w);
+  // n == 0 launches too: one block, out3 = {correction, 0, 0}
+  const auto launch = states == 4 ? plfx::launch_edge_derivatives_psr : plfx::launch_edge_derivatives_psr_prot;
+  hipError_t e = launch(dtype, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t, scaler_sums, nsums, w->lnl_partials,
+                        w->lnl_ticket, out3, site_lnl, ctx->max_blocks, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "edge_derivatives_psr launch");
+  return PLFX_OK;
 }
 
 int plfx_edge_optimize_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *sumtab, int64_t n,
@@ -1446,8 +1371,13 @@ int plfx_edge_optimize_psr_gen(plfx_ctx *ctx, int dtype, int states, const void 
                                double *t_opt, double *out3_host, int *evals, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_edge_optimize(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin, tmax,
-                           max_evals, t_opt, out3_host, evals, stream);
+  if (int rc = check_psr_edge_args(ctx, dtype, sumtab, n, eigen, rates, ncat, rate_cat); rc != PLFX_OK) return rc;
+  return edge_newton_loop(ctx, "edge_optimize_psr", t0, tmin, tmax, max_evals, t_opt, out3_host, evals, pick(stream),
+                          [&](const double *d_t, double *d_out) {
+                            return plfx_edge_derivatives_psr_gen(ctx, dtype, states, sumtab, n, eigen, rates, ncat,
+                                                                 rate_cat, wgt, d_t, nullptr, 0, d_out, nullptr,
+                                                                 stream);
+                          });
 }
 
 int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const void *const *sumtabs, int nedges,
@@ -1457,8 +1387,16 @@ int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const v
                                    void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
-  return psr_edge_optimize_dev(ctx, dtype, states, sumtabs, nedges, n, eigen, rates, ncat, rate_cat, wgt, t0, tmin,
-                               tmax, max_evals, t_opt, out3, evals, stream);
+  // the groups run in the regions and under the ordering rule of plfx_edge_optimize_dev
+  const auto launch_group = states == 4 ? plfx::launch_edge_optimize_psr : plfx::launch_edge_optimize_psr_prot;
+  return edge_optimize_dev(
+      ctx, "edge_optimize_psr_dev", sumtabs, nedges, t0, tmin, tmax, max_evals, t_opt, stream,
+      [&](const void *st) { return check_psr_edge_args(ctx, dtype, st, n, eigen, rates, ncat, rate_cat); },
+      [&](int g, int c, StreamWs *w, hipStream_t s) {
+        return launch_group(dtype, sumtabs + g, c, n, eigen, rates, ncat, rate_cat, wgt, t0 + g, tmin, tmax, max_evals,
+                            w->edge_state, w->lnl_partials, w->ws, t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
+                            evals ? evals + g : nullptr, ctx->max_blocks, s);
+      });
 }
 
 // ---- (12) the PSR rate scan ----

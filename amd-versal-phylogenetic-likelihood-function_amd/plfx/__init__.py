@@ -21,6 +21,7 @@ call raises ``PlfxError``.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from pathlib import Path
 
@@ -191,34 +192,25 @@ def load():
                                      dp, dp, C.POINTER(i32), vp]
     L.plfx_edge_optimize_dev.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl,
                                          i32, vp, vp, vp, vp]
-    L.plfx_plf_psr_dev.argtypes = [vp, i32, C.POINTER(PsrNode), i32, vp, i64, vp, i32, vp, vp, vp]
-    L.plfx_root_lnl_psr.argtypes = [vp, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
-    L.plfx_edge_sumtable_psr.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, vp]
-    L.plfx_edge_derivatives_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.plfx_edge_optimize_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32, dp, dp,
-                                         C.POINTER(i32), vp]
-    L.plfx_traverse_psr.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, vp,
-                                    i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
-    L.plfx_edge_optimize_psr_dev.argtypes = [vp, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl, i32,
-                                             vp, vp, vp, vp]
-    L.plfx_edge_sumtable_psr_batch.argtypes = [vp, i32, C.POINTER(PsrEdge), i32, i64, vp, vp]
+    # the per-site-rate entries (the arguments after ctx and dtype) and their _gen twins, which take states first
+    pvp, top, dbl3 = C.POINTER(vp), C.POINTER(TravOp), [dbl, dbl, dbl]
+    for name, args in (
+            ("plfx_plf_psr_dev", [C.POINTER(PsrNode), i32, vp, i64, vp, i32, vp, vp, vp]),
+            ("plfx_traverse_psr", [top, i32, pvp, pvp, i32, vp, i32, vp, i64, vp, i32, vp, pvp, vp, vp, vp]),
+            ("plfx_root_lnl_psr", [vp, i64, vp, vp, vp, i32, vp, vp, vp]),
+            ("plfx_edge_sumtable_psr", [vp, vp, vp, i64, vp, vp, vp]),
+            ("plfx_edge_sumtable_psr_batch", [C.POINTER(PsrEdge), i32, i64, vp, vp]),
+            ("plfx_edge_derivatives_psr", [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+            ("plfx_edge_optimize_psr", [vp, i64, vp, vp, i32, vp, vp] + dbl3 + [i32, dp, dp, C.POINTER(i32), vp]),
+            ("plfx_edge_optimize_psr_dev", [pvp, i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp])):
+        getattr(L, name).argtypes = [vp, i32] + args
+        getattr(L, name + "_gen").argtypes = [vp, i32, i32] + args
     L.plfx_site_lnl_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, i64, vp, vp]
     L.plfx_psr_rate_scan.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, i32,
                                      i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.plfx_psr_rate_scan_workspace.argtypes = [i32, i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)]
     L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
-    L.plfx_plf_psr_dev_gen.argtypes = [vp, i32, i32, C.POINTER(PsrNode), i32, vp, i64, vp, i32, vp, vp, vp]
-    L.plfx_traverse_psr_gen.argtypes = [vp, i32, i32, C.POINTER(TravOp), i32, C.POINTER(vp), C.POINTER(vp), i32, vp,
-                                        i32, vp, i64, vp, i32, vp, C.POINTER(vp), vp, vp, vp]
-    L.plfx_root_lnl_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
     L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
-    L.plfx_edge_sumtable_psr_gen.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, vp, vp]
-    L.plfx_edge_sumtable_psr_batch_gen.argtypes = [vp, i32, i32, C.POINTER(PsrEdge), i32, i64, vp, vp]
-    L.plfx_edge_derivatives_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.plfx_edge_optimize_psr_gen.argtypes = [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, dbl, dbl, dbl, i32, dp, dp,
-                                             C.POINTER(i32), vp]
-    L.plfx_edge_optimize_psr_dev_gen.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i64, vp, vp, i32, vp, vp, vp, dbl,
-                                                 dbl, i32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -305,6 +297,15 @@ class Context:
     def _check(self, rc):
         if rc != OK:
             raise PlfxError(rc, self._L.plfx_last_error(self.h).decode(errors="replace"))
+
+    def _call(self, name, dt, states, psr, gen, *args):
+        """Call the C entry `name` on tensors of dtype dt.  A Gamma entry takes
+        the state count after the dtype; a per-site-rate entry (psr) is
+        `name`, or with gen its _gen twin, which alone takes the state count."""
+        import torch
+
+        fn = getattr(self._L, name + ("_gen" if psr and gen else ""))
+        self._check(fn(self.h, F32 if dt == torch.float32 else F64, *((states,) if gen or not psr else ()), *args))
 
     # -- (1) plf() drop-in on host arrays ----------------------------------
     def plf(self, x1_start, x2_start, x3_start, EV, n, left, right, wgt=None):
@@ -624,68 +625,67 @@ class Context:
     def root_lnl(self, x, n, out, catw=None, freq=None, wgt=None, scaler_sums=None,
                  site_lnl=None, states=4, stream=None):
         """Root lnL into `out` (float64 device tensor, 1 element); see plfx.h (7)."""
-        self._root_lnl(False, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream)
+        self._root_lnl(False, False, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream)
 
-    def _root_lnl(self, psr, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream):
-        """root_lnl (4 * states values per site) and root_lnl_psr (states)."""
+    def _root_lnl(self, psr, gen, states, x, n, out, catw, freq, wgt, scaler_sums, site_lnl, stream):
+        """root_lnl (4 * states values per site) and root_lnl_psr[_gen] (states)."""
         import torch
 
+        if psr:
+            states = self._psr_states(gen, states)
         _tensor(out, "out", torch.float64, 1, contiguous=False)
         _tensor(x, "x", (torch.float32, torch.float64), (1 if psr else 4) * states * n)
         for k, t, m in (("catw", catw, 4), ("freq", freq, states), ("site_lnl", site_lnl, n)):
             _tensor(t, k, torch.float64, m, optional=True)
         _check_aux(n, wgt, None, None)
         _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
-        p = _ptr
-        dt = F32 if x.dtype == torch.float32 else F64
-        tail = (p(freq), p(wgt), p(scaler_sums), 0 if scaler_sums is None else scaler_sums.numel(), p(out),
-                p(site_lnl), self._sh(stream))
-        if psr:
-            self._check(self._L.plfx_root_lnl_psr(self.h, dt, p(x), int(n), *tail))
-        else:
-            self._check(self._L.plfx_root_lnl(self.h, dt, states, p(x), int(n), p(catw), *tail))
+        nsums = 0 if scaler_sums is None else scaler_sums.numel()
+        self._call("plfx_root_lnl_psr" if psr else "plfx_root_lnl", x.dtype, states, psr, gen, _ptr(x), int(n),
+                   *(() if psr else (_ptr(catw),)), _ptr(freq), _ptr(wgt), _ptr(scaler_sums), nsums, _ptr(out),
+                   _ptr(site_lnl), self._sh(stream))
 
     # -- (10) one branch between two fixed CLVs -----------------------------
     def edge_sumtable(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
         """sumtab = x1 * x2 elementwise (plfx.h (10)); side 1 is the dense CLV
         x1 or the uint8 codes tip1 with the eigen-convention table tipvec
         (16 x 4 DNA, PROT_CODES x 20 protein).  CLVs in the eigen convention."""
-        self._edge_sumtable(False, states, x2, sumtab, n, x1, tip1, tipvec, stream)
+        self._edge_sumtable(False, False, states, x2, sumtab, n, x1, tip1, tipvec, stream)
 
-    def _edge_sumtable(self, psr, states, x2, sumtab, n, x1, tip1, tipvec, stream):
-        """edge_sumtable (4 * states values per site) and edge_sumtable_psr (states)."""
+    def _edge_sumtable(self, psr, gen, states, x2, sumtab, n, x1, tip1, tipvec, stream):
+        """edge_sumtable (4 * states values per site) and edge_sumtable_psr[_gen] (states)."""
         import torch
 
+        if psr:
+            states = self._psr_states(gen, states)
         dt = sumtab.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
         for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
             _tensor(t, k, dt, (1 if psr else 4) * states * n, optional=True)
         _tensor(tip1, "tip1", torch.uint8, n, optional=True)
-        p = _ptr
-        tail = (p(tip1), p(x1), p(x2), int(n), self._tipvec(tipvec, dt, states), p(sumtab), self._sh(stream))
-        if psr:
-            self._check(self._L.plfx_edge_sumtable_psr(self.h, F32 if dt == torch.float32 else F64, *tail))
-        else:
-            self._check(self._L.plfx_edge_sumtable(self.h, F32 if dt == torch.float32 else F64, int(states), *tail))
+        self._call("plfx_edge_sumtable_psr" if psr else "plfx_edge_sumtable", dt, int(states), psr, gen, _ptr(tip1),
+                   _ptr(x1), _ptr(x2), int(n), self._tipvec(tipvec, dt, states), _ptr(sumtab), self._sh(stream))
 
-    def _edge_args(self, sumtab, n, eigen, rates, catw, wgt, states, rate_cat=None, psr=False):
-        """The arguments the Gamma edge calls share (4 * states values per
-        site, catw) and, with psr, the per-site-rate ones (states, rate_cat)."""
+    def _edge_args(self, name, psr, gen, states, sumtab, n, eigen, rates, cat, wgt):
+        """What the edge calls share, checked: the Gamma ones (4 * states values
+        per site, cat = catw) and the per-site-rate ones (psr: states values,
+        cat = rate_cat).  name: the C entry, with %s where its PSR form has
+        _psr.  Returns (call, tail): call(table(s), *tail, ...) is the call."""
         import torch
 
+        if psr:
+            states = self._psr_states(gen, states)
         _tensor(sumtab, "sumtab", (torch.float32, torch.float64), (1 if psr else 4) * states * n)
         ncat = rates.numel()
         _tensor(eigen, "eigen", torch.float64, states, optional=True)
         _tensor(rates, "rates", torch.float64, 1)
         if psr:
-            self._psr_cats(rate_cat, n)
+            _tensor(cat, "rate_cat", torch.uint8, n)
         else:
-            _tensor(catw, "catw", torch.float64, ncat, optional=True)
+            _tensor(cat, "catw", torch.float64, ncat, optional=True)
         _check_aux(n, wgt, None, None)
-        p = _ptr
-        head = (self.h, F32 if sumtab.dtype == torch.float32 else F64) + (() if psr else (int(states),))
-        return head + (p(sumtab), int(n), p(eigen), p(rates), ncat, p(rate_cat if psr else catw), p(wgt))
+        call = functools.partial(self._call, name % ("_psr" if psr else ""), sumtab.dtype, int(states), psr, gen)
+        return call, (int(n), _ptr(eigen), _ptr(rates), ncat, _ptr(cat), _ptr(wgt))
 
     def edge_derivatives(self, sumtab, n, eigen, rates, t, out, catw=None, wgt=None, scaler_sums=None,
                          site_lnl=None, states=4, stream=None):
@@ -693,21 +693,22 @@ class Context:
         the branch whose sum table is `sumtab`, at the branch length in the
         device double `t`; see plfx.h (10).  eigen, rates: the device arrays
         pmatrix() takes."""
-        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
-        self._edge_derivatives(self._L.plfx_edge_derivatives, args, n, t, out, scaler_sums, site_lnl, stream)
+        self._edge_derivatives(False, False, states, sumtab, n, eigen, rates, catw, wgt, t, out, scaler_sums,
+                               site_lnl, stream)
 
-    def _edge_derivatives(self, fn, args, n, t, out, scaler_sums, site_lnl, stream):
-        """edge_derivatives and edge_derivatives_psr after their _edge_args."""
+    def _edge_derivatives(self, psr, gen, states, sumtab, n, eigen, rates, cat, wgt, t, out, scaler_sums, site_lnl,
+                          stream):
+        """edge_derivatives and edge_derivatives_psr[_gen] after their _edge_args."""
         import torch
 
+        call, tail = self._edge_args("plfx_edge_derivatives%s", psr, gen, states, sumtab, n, eigen, rates, cat, wgt)
         for k, x, m in (("t", t, 1), ("out", out, 3), ("site_lnl", site_lnl, n)):
             _tensor(x, k, torch.float64, m, optional=True)
         if t is None or out is None:
             raise PlfxError(ERR_INVALID, "t and out are required")
         _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
-        p = _ptr
         nsums = 0 if scaler_sums is None else scaler_sums.numel()
-        self._check(fn(*args, p(t), p(scaler_sums), nsums, p(out), p(site_lnl), self._sh(stream)))
+        call(_ptr(sumtab), *tail, _ptr(t), _ptr(scaler_sums), nsums, _ptr(out), _ptr(site_lnl), self._sh(stream))
 
     def optimize_branch(self, sumtab, n, eigen, rates, t0, tmin=1e-8, tmax=10.0, max_evals=64,
                         catw=None, wgt=None, states=4, stream=None):
@@ -715,10 +716,15 @@ class Context:
         bracketed Newton iteration of plfx_edge_optimize from t0 (host-
         synchronous).  Returns (t, lnL, d1, d2, evals), lnL without a scaling
         correction."""
-        args = self._edge_args(sumtab, n, eigen, rates, catw, wgt, states)
+        return self._optimize_branch(False, False, states, sumtab, n, eigen, rates, catw, wgt, t0, tmin, tmax,
+                                     max_evals, stream)
+
+    def _optimize_branch(self, psr, gen, states, sumtab, n, eigen, rates, cat, wgt, t0, tmin, tmax, max_evals, stream):
+        """optimize_branch and optimize_branch_psr[_gen] after their _edge_args."""
+        call, tail = self._edge_args("plfx_edge_optimize%s", psr, gen, states, sumtab, n, eigen, rates, cat, wgt)
         t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
-        self._check(self._L.plfx_edge_optimize(*args, float(t0), float(tmin), float(tmax), int(max_evals),
-                                               C.byref(t), out, C.byref(ev), self._sh(stream)))
+        call(_ptr(sumtab), *tail, float(t0), float(tmin), float(tmax), int(max_evals), C.byref(t), out, C.byref(ev),
+             self._sh(stream))
         return t.value, out[0], out[1], out[2], ev.value
 
     def optimize_branches(self, sumtabs, n, eigen, rates, t0, t_opt, tmin=1e-8, tmax=10.0, max_evals=64,
@@ -729,6 +735,12 @@ class Context:
         safe.  t0, t_opt: float64 device tensors of len(sumtabs) (t0 is read
         on the device: another call's t_opt may be passed); out3 (3 per
         branch, float64) and evals (int32) are optional device tensors."""
+        self._optimize_branches(False, False, states, sumtabs, n, eigen, rates, catw, wgt, t0, t_opt, tmin, tmax,
+                                max_evals, out3, evals, stream)
+
+    def _optimize_branches(self, psr, gen, states, sumtabs, n, eigen, rates, cat, wgt, t0, t_opt, tmin, tmax,
+                           max_evals, out3, evals, stream):
+        """optimize_branches and optimize_branches_psr[_gen] after their _edge_args."""
         import torch
 
         m = len(sumtabs)
@@ -737,28 +749,24 @@ class Context:
         for st in sumtabs:
             if st.dtype != sumtabs[0].dtype:
                 raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
-            args = self._edge_args(st, n, eigen, rates, catw, wgt, states)
+            call, tail = self._edge_args("plfx_edge_optimize%s_dev", psr, gen, states, st, n, eigen, rates, cat, wgt)
         for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
                               ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
             _tensor(x, k, dt, cnt, optional=True)
         if t0 is None or t_opt is None:
             raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
-        p = _ptr
         tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
-        self._check(self._L.plfx_edge_optimize_dev(*args[:3], tabs, m, *args[4:], p(t0), float(tmin), float(tmax),
-                                                   int(max_evals), p(t_opt), p(out3), p(evals), self._sh(stream)))
+        call(tabs, m, *tail, _ptr(t0), float(tmin), float(tmax), int(max_evals), _ptr(t_opt), _ptr(out3), _ptr(evals),
+             self._sh(stream))
 
-    # -- (11) per-site rate categories ---------------------------------------
+    # -- (11) per-site rate categories; (11b, 11c) the _gen twins, with a state count: one body each, taking gen --
     @staticmethod
-    def _psr_states(states):
-        if states != 4:
-            raise PlfxError(ERR_UNSUPPORTED, f"per-site rate categories: states={states} not built (4)")
-
-    @staticmethod
-    def _psr_cats(rate_cat, n):
-        import torch
-
-        _tensor(rate_cat, "rate_cat", torch.uint8, n)
+    def _psr_states(gen, states):
+        """The state counts built: 4 alone through the section-11 entries, 4 and 20 through their _gen twins."""
+        if states not in ((4, 20) if gen else (4,)):
+            raise PlfxError(ERR_UNSUPPORTED,
+                            f"per-site rate categories: states={states} not built ({'4, 20' if gen else '4'})")
+        return int(states)
 
     def plf_psr(self, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, states=4, stream=None):
         """Per-site-rate node updates (plfx.h section 11).  nodes: one dict or
@@ -767,71 +775,7 @@ class Context:
         codes), plus optional scaler, scaler_sum.  rate_cat: uint8 device
         tensor, one category per site (values >= ncat count as ncat - 1);
         left / right hold ncat * 16 values."""
-        import torch
-
-        self._psr_states(states)
-        if isinstance(nodes, dict):
-            nodes = [nodes]
-        n, ncat = int(n), int(ncat)
-        dt = EV.dtype
-        if dt not in (torch.float32, torch.float64):
-            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        _tensor(EV, "EV", dt, 16, contiguous=False)
-        self._psr_cats(rate_cat, n)
-        _check_aux(n, wgt, None, None)
-        arr = (PsrNode * max(1, len(nodes)))()
-        for i, nd in enumerate(nodes):
-            for k in ("x1", "x2", "x3"):
-                _tensor(nd.get(k), k, dt, 4 * n, optional=True)
-            for k in ("tip1", "tip2"):
-                _tensor(nd.get(k), k, torch.uint8, n, optional=True)
-            for k in ("left", "right"):
-                _tensor(nd.get(k), k, dt, 16 * max(ncat, 0), optional=True)
-            _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
-            arr[i] = PsrNode(*(_ptr(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
-                                                          "scaler", "scaler_sum")))
-        self._check(self._L.plfx_plf_psr_dev(
-            self.h, F32 if dt == torch.float32 else F64, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
-            _ptr(wgt), self._tipvec(tipvec, dt), self._sh(stream)))
-
-    def traverse_psr(self, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None, scaler_sums=None,
-                     stream=None, tips=None, tipvec=None, states=4):
-        """A post-order traversal under per-site rate categories (plfx.h
-        section 11, plfx_traverse_psr).  ops, clv, tips, scalers, scaler_sums
-        as traverse(); a CLV slot holds 4*n values; pmats holds whole (left,
-        right) pairs of ncat * 16 values each, as pmatrix() writes them for
-        2*npmats branches and ncat rates; rate_cat, ncat, tipvec as plf_psr().
-        Level pairs are fused only in a context created with PLFX_FUSE >= 1
-        in the environment.  last_schedule() reports the call: triples,
-        unfused, launches."""
-        import torch
-
-        self._psr_states(states)
-        n, ncat = int(n), int(ncat)
-        dt = EV.dtype
-        if dt not in (torch.float32, torch.float64):
-            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        top, nops, slots, tp, nslots, npmats, sc = self._traverse_args(
-            ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, 4, 16 * max(ncat, 1), 16)
-        self._psr_cats(rate_cat, n)
-        self._check(self._L.plfx_traverse_psr(
-            self.h, F32 if dt == torch.float32 else F64, top, nops, slots, tp, nslots, _ptr(pmats), npmats,
-            _ptr(EV), n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt),
-            self._sh(stream)))
-
-    def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
-                     stream=None):
-        """Root lnL of a per-site-rate CLV into `out` (float64 device tensor,
-        1 element); plfx.h section 11."""
-        self._psr_states(states)
-        self._root_lnl(True, states, x, n, out, None, freq, wgt, scaler_sums, site_lnl, stream)
-
-    # -- (11b) per-site rate categories with a state count -------------------
-    @staticmethod
-    def _psr_gen_states(states):
-        if states not in (4, 20):
-            raise PlfxError(ERR_UNSUPPORTED, f"per-site rate categories: states={states} not built (4, 20)")
-        return int(states)
+        self._plf_psr(False, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream)
 
     def plf_psr_gen(self, states, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, stream=None):
         """plf_psr() with a state count (plfx.h section 11b): states 4 is
@@ -839,9 +783,12 @@ class Context:
         left / right of ncat * 400, EV of 400, uint8 protein codes (PROT_CODES
         rows of 20 in tipvec, None = the default table).  Fast when the sites
         are sorted by category: see psr_site_order()."""
+        self._plf_psr(True, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream)
+
+    def _plf_psr(self, gen, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream):
         import torch
 
-        S = self._psr_gen_states(states)
+        S = self._psr_states(gen, states)
         if isinstance(nodes, dict):
             nodes = [nodes]
         n, ncat = int(n), int(ncat)
@@ -849,7 +796,7 @@ class Context:
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
         _tensor(EV, "EV", dt, S * S, contiguous=False)
-        self._psr_cats(rate_cat, n)
+        _tensor(rate_cat, "rate_cat", torch.uint8, n)
         _check_aux(n, wgt, None, None)
         arr = (PsrNode * max(1, len(nodes)))()
         for i, nd in enumerate(nodes):
@@ -862,9 +809,21 @@ class Context:
             _check_aux(n, None, nd.get("scaler"), nd.get("scaler_sum"))
             arr[i] = PsrNode(*(_ptr(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
                                                           "scaler", "scaler_sum")))
-        self._check(self._L.plfx_plf_psr_dev_gen(
-            self.h, F32 if dt == torch.float32 else F64, S, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
-            _ptr(wgt), self._tipvec(tipvec, dt, S), self._sh(stream)))
+        self._call("plfx_plf_psr_dev", dt, S, True, gen, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
+                   _ptr(wgt), self._tipvec(tipvec, dt, S), self._sh(stream))
+
+    def traverse_psr(self, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None, scaler_sums=None,
+                     stream=None, tips=None, tipvec=None, states=4):
+        """A post-order traversal under per-site rate categories (plfx.h
+        section 11, plfx_traverse_psr).  ops, clv, tips, scalers, scaler_sums
+        as traverse(); a CLV slot holds 4*n values; pmats holds whole (left,
+        right) pairs of ncat * 16 values each, as pmatrix() writes them for
+        2*npmats branches and ncat rates; rate_cat, ncat, tipvec as plf_psr().
+        Level pairs are fused only in a context created with PLFX_FUSE >= 1
+        in the environment.  last_schedule() reports the call: triples,
+        unfused, launches."""
+        self._traverse_psr(False, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt, scalers, scaler_sums, stream,
+                           tips, tipvec)
 
     def traverse_psr_gen(self, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None,
                          scaler_sums=None, stream=None, tips=None, tipvec=None):
@@ -872,65 +831,66 @@ class Context:
         states 20 a CLV slot holds 20*n values, pmats whole (left, right) pairs
         of ncat * 400 values each, and no level pair is fused whatever
         PLFX_FUSE says: last_schedule() reports triples 0, unfused = the ops."""
+        self._traverse_psr(True, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt, scalers, scaler_sums, stream,
+                           tips, tipvec)
+
+    def _traverse_psr(self, gen, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt, scalers, scaler_sums, stream,
+                      tips, tipvec):
         import torch
 
-        S = self._psr_gen_states(states)
+        S = self._psr_states(gen, states)
         n, ncat = int(n), int(ncat)
         dt = EV.dtype
         if dt not in (torch.float32, torch.float64):
             raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
         top, nops, slots, tp, nslots, npmats, sc = self._traverse_args(
             ops, clv, pmats, EV, n, wgt, scalers, scaler_sums, tips, S, S * S * max(ncat, 1), S * S)
-        self._psr_cats(rate_cat, n)
-        self._check(self._L.plfx_traverse_psr_gen(
-            self.h, F32 if dt == torch.float32 else F64, S, top, nops, slots, tp, nslots, _ptr(pmats), npmats,
-            _ptr(EV), n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt, S),
-            self._sh(stream)))
+        _tensor(rate_cat, "rate_cat", torch.uint8, n)
+        self._call("plfx_traverse_psr", dt, S, True, gen, top, nops, slots, tp, nslots, _ptr(pmats), npmats, _ptr(EV),
+                   n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt, S),
+                   self._sh(stream))
+
+    def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
+                     stream=None):
+        """Root lnL of a per-site-rate CLV into `out` (float64 device tensor,
+        1 element); plfx.h section 11."""
+        self._root_lnl(True, False, states, x, n, out, None, freq, wgt, scaler_sums, site_lnl, stream)
 
     def root_lnl_psr_gen(self, states, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None,
                          stream=None):
         """root_lnl_psr() with a state count (plfx.h section 11b): states
         values per site, freq None = 1/states each."""
-        import torch
+        self._root_lnl(True, True, states, x, n, out, None, freq, wgt, scaler_sums, site_lnl, stream)
 
-        S = self._psr_gen_states(states)
-        _tensor(out, "out", torch.float64, 1, contiguous=False)
-        _tensor(x, "x", (torch.float32, torch.float64), S * n)
-        for k, t, m in (("freq", freq, S), ("site_lnl", site_lnl, n)):
-            _tensor(t, k, torch.float64, m, optional=True)
-        _check_aux(n, wgt, None, None)
-        _tensor(scaler_sums, "scaler_sums", torch.int64, 0, optional=True)
-        p = _ptr
-        self._check(self._L.plfx_root_lnl_psr_gen(
-            self.h, F32 if x.dtype == torch.float32 else F64, S, p(x), int(n), p(freq), p(wgt), p(scaler_sums),
-            0 if scaler_sums is None else scaler_sums.numel(), p(out), p(site_lnl), self._sh(stream)))
+    def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
+        """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the
+        dense CLV x1 or the uint8 codes tip1 with the eigen-convention table."""
+        self._edge_sumtable(True, False, states, x2, sumtab, n, x1, tip1, tipvec, stream)
 
-    # -- (11c) the branch-length half with a state count ---------------------
     def edge_sumtable_psr_gen(self, states, x2, sumtab, n, x1=None, tip1=None, tipvec=None, stream=None):
         """edge_sumtable_psr() with a state count (plfx.h section 11c): states
         4 is edge_sumtable_psr() itself; with states 20 the CLVs and the table
         hold 20*n values and tip1 holds protein codes (row min(code, 23) of the
         PROT_CODES x 20 eigen-convention tipvec)."""
-        import torch
+        self._edge_sumtable(True, True, states, x2, sumtab, n, x1, tip1, tipvec, stream)
 
-        S = self._psr_gen_states(states)
-        dt = sumtab.dtype
-        if dt not in (torch.float32, torch.float64):
-            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        for k, t in (("x1", x1), ("x2", x2), ("sumtab", sumtab)):
-            _tensor(t, k, dt, S * n, optional=True)
-        _tensor(tip1, "tip1", torch.uint8, n, optional=True)
-        p = _ptr
-        self._check(self._L.plfx_edge_sumtable_psr_gen(
-            self.h, F32 if dt == torch.float32 else F64, S, p(tip1), p(x1), p(x2), int(n),
-            self._tipvec(tipvec, dt, S), p(sumtab), self._sh(stream)))
+    def edge_sumtables_psr(self, edges, n, tipvec=None, states=4, stream=None):
+        """The sum tables of many per-site-rate branches in one call
+        (plfx_edge_sumtable_psr_batch).  edges: a list of dicts with x2,
+        sumtab and exactly one of x1 / tip1, as edge_sumtable_psr's arguments;
+        every table of the call must be apart from every other table and
+        from every input, inputs may repeat."""
+        self._edge_sumtables_psr(False, states, edges, n, tipvec, stream)
 
     def edge_sumtables_psr_gen(self, states, edges, n, tipvec=None, stream=None):
         """edge_sumtables_psr() with a state count (plfx_edge_sumtable_psr_batch_gen):
         every CLV and table holds states*n values."""
+        self._edge_sumtables_psr(True, states, edges, n, tipvec, stream)
+
+    def _edge_sumtables_psr(self, gen, states, edges, n, tipvec, stream):
         import torch
 
-        S = self._psr_gen_states(states)
+        S = self._psr_states(gen, states)
         if isinstance(edges, dict):
             edges = [edges]
         n = int(n)
@@ -943,85 +903,38 @@ class Context:
                 _tensor(e.get(k), k, dt, S * n, optional=True)
             _tensor(e.get("tip1"), "tip1", torch.uint8, n, optional=True)
             arr[i] = PsrEdge(*(_ptr(e.get(k)) for k in ("tip1", "x1", "x2", "sumtab")))
-        self._check(self._L.plfx_edge_sumtable_psr_batch_gen(
-            self.h, F32 if dt == torch.float32 else F64, S, arr, len(edges), n, self._tipvec(tipvec, dt, S),
-            self._sh(stream)))
-
-    def _edge_args_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, wgt):
-        """(ctx, dtype, states, sumtab, n, eigen, rates, ncat, rate_cat, wgt) of the section-11c calls."""
-        S = self._psr_gen_states(states)
-        a = self._edge_args(sumtab, n, eigen, rates, None, wgt, S, rate_cat, psr=True)
-        return a[:2] + (S,) + a[2:]
-
-    def edge_derivatives_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None,
-                                 scaler_sums=None, site_lnl=None, stream=None):
-        """edge_derivatives_psr() with a state count (plfx.h section 11c): with
-        states 20 the table holds 20*n values and eigen is what
-        pmatrix(states=20) takes."""
-        args = self._edge_args_psr_gen(states, sumtab, n, eigen, rates, rate_cat, wgt)
-        self._edge_derivatives(self._L.plfx_edge_derivatives_psr_gen, args, n, t, out, scaler_sums, site_lnl, stream)
-
-    def optimize_branch_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0,
-                                max_evals=64, wgt=None, stream=None):
-        """optimize_branch_psr() with a state count (plfx_edge_optimize_psr_gen,
-        host-synchronous).  Returns (t, lnL, d1, d2, evals)."""
-        args = self._edge_args_psr_gen(states, sumtab, n, eigen, rates, rate_cat, wgt)
-        t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
-        self._check(self._L.plfx_edge_optimize_psr_gen(*args, float(t0), float(tmin), float(tmax), int(max_evals),
-                                                       C.byref(t), out, C.byref(ev), self._sh(stream)))
-        return t.value, out[0], out[1], out[2], ev.value
-
-    def optimize_branches_psr_gen(self, states, sumtabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=1e-8,
-                                  tmax=10.0, max_evals=64, out3=None, evals=None, wgt=None, stream=None):
-        """optimize_branches_psr() with a state count (plfx_edge_optimize_psr_dev_gen):
-        asynchronous, capture-safe; sumtabs: device tensors of states*n values each."""
-        import torch
-
-        m = len(sumtabs)
-        if m < 1:
-            raise PlfxError(ERR_INVALID, "sumtabs must hold at least one sum table")
-        for st in sumtabs:
-            if st.dtype != sumtabs[0].dtype:
-                raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
-            args = self._edge_args_psr_gen(states, st, n, eigen, rates, rate_cat, wgt)
-        for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
-                              ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
-            _tensor(x, k, dt, cnt, optional=True)
-        if t0 is None or t_opt is None:
-            raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
-        p = _ptr
-        tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
-        self._check(self._L.plfx_edge_optimize_psr_dev_gen(*args[:3], tabs, m, *args[4:], p(t0), float(tmin),
-                                                           float(tmax), int(max_evals), p(t_opt), p(out3), p(evals),
-                                                           self._sh(stream)))
-
-    def edge_sumtable_psr(self, x2, sumtab, n, x1=None, tip1=None, tipvec=None, states=4, stream=None):
-        """sumtab = x1 * x2 over 4*n values (plfx.h section 11); side 1 is the
-        dense CLV x1 or the uint8 codes tip1 with the eigen-convention table."""
-        self._psr_states(states)
-        self._edge_sumtable(True, states, x2, sumtab, n, x1, tip1, tipvec, stream)
-
-    def _edge_args_psr(self, sumtab, n, eigen, rates, rate_cat, wgt, states):
-        self._psr_states(states)
-        return self._edge_args(sumtab, n, eigen, rates, None, wgt, states, rate_cat, psr=True)
+        self._call("plfx_edge_sumtable_psr_batch", dt, S, True, gen, arr, len(edges), n, self._tipvec(tipvec, dt, S),
+                   self._sh(stream))
 
     def edge_derivatives_psr(self, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None, scaler_sums=None,
                              site_lnl=None, states=4, stream=None):
         """out (float64 device tensor, 3 elements) = lnL, d lnL/dt, d2 lnL/dt2 of
         the per-site-rate branch whose sum table is `sumtab`, at the device
         double `t`; rates holds the ncat category rates (plfx.h section 11)."""
-        args = self._edge_args_psr(sumtab, n, eigen, rates, rate_cat, wgt, states)
-        self._edge_derivatives(self._L.plfx_edge_derivatives_psr, args, n, t, out, scaler_sums, site_lnl, stream)
+        self._edge_derivatives(True, False, states, sumtab, n, eigen, rates, rate_cat, wgt, t, out, scaler_sums,
+                               site_lnl, stream)
+
+    def edge_derivatives_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t, out, wgt=None,
+                                 scaler_sums=None, site_lnl=None, stream=None):
+        """edge_derivatives_psr() with a state count (plfx.h section 11c): with
+        states 20 the table holds 20*n values and eigen is what
+        pmatrix(states=20) takes."""
+        self._edge_derivatives(True, True, states, sumtab, n, eigen, rates, rate_cat, wgt, t, out, scaler_sums,
+                               site_lnl, stream)
 
     def optimize_branch_psr(self, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0, max_evals=64,
                             wgt=None, states=4, stream=None):
         """optimize_branch for a per-site-rate branch (plfx_edge_optimize_psr,
         host-synchronous).  Returns (t, lnL, d1, d2, evals)."""
-        args = self._edge_args_psr(sumtab, n, eigen, rates, rate_cat, wgt, states)
-        t, out, ev = C.c_double(0.0), (C.c_double * 3)(), C.c_int(0)
-        self._check(self._L.plfx_edge_optimize_psr(*args, float(t0), float(tmin), float(tmax), int(max_evals),
-                                                   C.byref(t), out, C.byref(ev), self._sh(stream)))
-        return t.value, out[0], out[1], out[2], ev.value
+        return self._optimize_branch(True, False, states, sumtab, n, eigen, rates, rate_cat, wgt, t0, tmin, tmax,
+                                     max_evals, stream)
+
+    def optimize_branch_psr_gen(self, states, sumtab, n, eigen, rates, rate_cat, t0, tmin=1e-8, tmax=10.0,
+                                max_evals=64, wgt=None, stream=None):
+        """optimize_branch_psr() with a state count (plfx_edge_optimize_psr_gen,
+        host-synchronous).  Returns (t, lnL, d1, d2, evals)."""
+        return self._optimize_branch(True, True, states, sumtab, n, eigen, rates, rate_cat, wgt, t0, tmin, tmax,
+                                     max_evals, stream)
 
     def optimize_branches_psr(self, sumtabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=1e-8, tmax=10.0,
                               max_evals=64, out3=None, evals=None, wgt=None, states=4, stream=None):
@@ -1029,50 +942,15 @@ class Context:
         device (plfx_edge_optimize_psr_dev): asynchronous, capture-safe.
         sumtabs: device tensors of 4*n values each; rate_cat, rates as
         edge_derivatives_psr; t0, t_opt, out3, evals as optimize_branches."""
-        import torch
+        self._optimize_branches(True, False, states, sumtabs, n, eigen, rates, rate_cat, wgt, t0, t_opt, tmin, tmax,
+                                max_evals, out3, evals, stream)
 
-        m = len(sumtabs)
-        if m < 1:
-            raise PlfxError(ERR_INVALID, "sumtabs must hold at least one sum table")
-        for st in sumtabs:
-            if st.dtype != sumtabs[0].dtype:
-                raise PlfxError(ERR_INVALID, "the sum tables must share one dtype")
-            args = self._edge_args_psr(st, n, eigen, rates, rate_cat, wgt, states)
-        for k, x, cnt, dt in (("t0", t0, m, torch.float64), ("t_opt", t_opt, m, torch.float64),
-                              ("out3", out3, 3 * m, torch.float64), ("evals", evals, m, torch.int32)):
-            _tensor(x, k, dt, cnt, optional=True)
-        if t0 is None or t_opt is None:
-            raise PlfxError(ERR_INVALID, "t0 and t_opt are required")
-        p = _ptr
-        tabs = (C.c_void_p * m)(*[st.data_ptr() for st in sumtabs])
-        self._check(self._L.plfx_edge_optimize_psr_dev(*args[:2], tabs, m, *args[3:], p(t0), float(tmin),
-                                                       float(tmax), int(max_evals), p(t_opt), p(out3), p(evals),
-                                                       self._sh(stream)))
-
-    def edge_sumtables_psr(self, edges, n, tipvec=None, states=4, stream=None):
-        """The sum tables of many per-site-rate branches in one call
-        (plfx_edge_sumtable_psr_batch).  edges: a list of dicts with x2,
-        sumtab and exactly one of x1 / tip1, as edge_sumtable_psr's arguments;
-        every table of the call must be apart from every other table and
-        from every input, inputs may repeat."""
-        import torch
-
-        self._psr_states(states)
-        if isinstance(edges, dict):
-            edges = [edges]
-        n = int(n)
-        dt = edges[0]["sumtab"].dtype if edges and edges[0].get("sumtab") is not None else torch.float64
-        if dt not in (torch.float32, torch.float64):
-            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
-        arr = (PsrEdge * max(1, len(edges)))()
-        for i, e in enumerate(edges):
-            for k in ("x1", "x2", "sumtab"):
-                _tensor(e.get(k), k, dt, 4 * n, optional=True)
-            _tensor(e.get("tip1"), "tip1", torch.uint8, n, optional=True)
-            arr[i] = PsrEdge(*(_ptr(e.get(k)) for k in ("tip1", "x1", "x2", "sumtab")))
-        self._check(self._L.plfx_edge_sumtable_psr_batch(
-            self.h, F32 if dt == torch.float32 else F64, arr, len(edges), n, self._tipvec(tipvec, dt),
-            self._sh(stream)))
+    def optimize_branches_psr_gen(self, states, sumtabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=1e-8,
+                                  tmax=10.0, max_evals=64, out3=None, evals=None, wgt=None, stream=None):
+        """optimize_branches_psr() with a state count (plfx_edge_optimize_psr_dev_gen):
+        asynchronous, capture-safe; sumtabs: device tensors of states*n values each."""
+        self._optimize_branches(True, True, states, sumtabs, n, eigen, rates, rate_cat, wgt, t0, t_opt, tmin, tmax,
+                                max_evals, out3, evals, stream)
 
     # -- (12) the PSR rate scan ----------------------------------------------
     def site_lnl_psr(self, x, n, site_lnl, freq=None, scalers=None, nsc=None, stride=None, states=4, stream=None):
@@ -1083,7 +961,7 @@ class Context:
         stride default to its shape; 1-D: pass both), or None for nsc = 0."""
         import torch
 
-        self._psr_states(states)
+        self._psr_states(False, states)
         n = int(n)
         _tensor(x, "x", (torch.float32, torch.float64), 4 * n)
         _tensor(site_lnl, "site_lnl", torch.float64, n)
@@ -1117,7 +995,7 @@ class Context:
         traversal (sizes the workspace; the outputs do not depend on it)."""
         import torch
 
-        self._psr_states(states)
+        self._psr_states(False, states)
         n, group = int(n), int(group)
         dt = EV.dtype
         if dt not in (torch.float32, torch.float64):
