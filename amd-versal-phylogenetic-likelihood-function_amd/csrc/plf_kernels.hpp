@@ -193,6 +193,16 @@ hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, 
                                          double tmax, int max_evals, void *state, double *partials,
                                          unsigned long long *ws, double *t_opt, double *out3, int32_t *evals,
                                          int max_blocks, hipStream_t s);
+// The protein rate scan (plfx.h section 12b; plf_psr_prot.hpp
+// psr_site_lnl_prot_kernel): launch_psr_site_lnl and launch_psr_scan_pass over
+// rows of 20 values, the same arguments.  The tiling is launch_psr_tile's.
+hipError_t launch_psr_site_lnl_prot(int dtype, const void *x, int64_t n, const double *freq, const uint8_t *scalers,
+                                    int nsc, int64_t stride, double *site_lnl, int max_blocks, hipStream_t s);
+hipError_t launch_psr_scan_pass_prot(int dtype, const void *x, int64_t n, int gc, const double *freq,
+                                     const uint8_t *scalers, int nsc, int64_t stride, int k0, bool first,
+                                     double *all_lnl, double *best_lnl, int32_t *best_idx, const int32_t *wgt,
+                                     double *partials, unsigned long long *ticket, double *out, int max_blocks,
+                                     hipStream_t s);
 
 hipError_t launch_scaler_sum(const uint8_t *scaler, const int32_t *wgt, int64_t n,
                              int64_t *out, unsigned long long *ws, int max_blocks,

@@ -1,7 +1,8 @@
 // plf_psr_prot.hip -- launchers of the protein per-site-rate kernels
 // (plf_psr_prot.hpp: the node and the root lnL with one rate category per site
 // and 20 states, plfx.h section 11b; the sum table -- one and batched --, the
-// edge sums and the branch-length loop on the device, section 11c).
+// edge sums and the branch-length loop on the device, section 11c; the rate
+// scan's per-site lnL and argmax, section 12b).
 //
 // Built into a library of its own, plfx/libplfx_psr_prot.so, which libplfx.so
 // links, as plf_psr.hip and plf_edge.hip are: the code objects of the other
@@ -158,6 +159,45 @@ hipError_t launch_edge_optimize_psr_prot(int dtype, const void *const *sumtabs, 
                             wgt, t0, tmin, tmax, max_evals, first, static_cast<EdgeNewtonStep *>(state), partials, ws,
                             t_opt, out3, evals);
             });
+      },
+      bools{dtype == 1});
+}
+
+// ---- plfx.h section 12b ----
+
+// launch_psr_site_lnl and launch_psr_scan_pass (plf_psr.hip) for rows of 20
+// values: one block per kBlock sites, capped at the co-resident blocks and,
+// for the pass that sums, at the partial slots of lnl_finish.
+hipError_t launch_psr_site_lnl_prot(int dtype, const void *x, int64_t n, const double *freq, const uint8_t *scalers,
+                                    int nsc, int64_t stride, double *site_lnl, int max_blocks, hipStream_t s) {
+  if (n < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::psr_site_lnl_prot_kernel<T, false>;
+        const int64_t gx = grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks);
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, 1, freq, scalers, nsc, stride, 0, 1,
+                      site_lnl, (double *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, (double *)nullptr,
+                      (unsigned long long *)nullptr, (double *)nullptr);
+      },
+      bools{dtype == 1});
+}
+
+hipError_t launch_psr_scan_pass_prot(int dtype, const void *x, int64_t n, int gc, const double *freq,
+                                     const uint8_t *scalers, int nsc, int64_t stride, int k0, bool first,
+                                     double *all_lnl, double *best_lnl, int32_t *best_idx, const int32_t *wgt,
+                                     double *partials, unsigned long long *ticket, double *out, int max_blocks,
+                                     hipStream_t s) {
+  if (n < 1 || gc < 1) return hipErrorInvalidValue;
+  return dispatch(
+      [&](auto k64) {
+        using T = real_t<k64()>;
+        static int cache = 0;
+        auto kernel = &dev::psr_site_lnl_prot_kernel<T, true>;
+        const int64_t gx = lnl_cap(grid_x((const void *)kernel, cache, n, kBlock, 1, max_blocks));
+        return launch(kernel, dim3((unsigned)gx), kBlock, s, (const T *)x, n, gc, freq, scalers, nsc, stride, k0,
+                      (int)first, all_lnl, best_lnl, best_idx, wgt, partials, ticket, out);
       },
       bools{dtype == 1});
 }

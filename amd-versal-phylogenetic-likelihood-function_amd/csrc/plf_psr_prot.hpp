@@ -35,7 +35,8 @@
 //
 // At the end of the file: the branch-length half (plfx.h section 11c) -- the
 // sum table, one and batched, the three edge sums and the branch-length loop
-// on the device, over tables of n * 20 values.
+// on the device, over tables of n * 20 values -- and the rate scan's per-site
+// lnL and argmax kernel (section 12b).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -623,6 +624,117 @@ edge_opt_psr_prot_kernel(const EdgeOptTabs tabs, int64_t n, const double *__rest
   edge_deriv_psr_prot_sites<T>(st, n, lambda, rates, ncat, rate_cat, wgt, t, part, nullptr, acc);
   if (lnl_finish<3, false>(acc, part, ws + (size_t)blockIdx.y * kWsWords, nullptr, nullptr, 0))
     edge_opt_step(sp, acc, t, tmin, tmax, max_evals, first, t_opt, out3, evals);
+}
+
+// ---- plfx.h section 12b: the protein per-site rate scan ----
+//
+// plf_psr.hpp's psr_site_lnl_kernel for rows of 20 values: per-site lnL with
+// the site's own scaling correction over a "virtual alignment" of G segments
+// of n sites (virtual site g * n + i = site i under candidate k0 + g), and the
+// running argmax over the candidates.  One lane owns site i, a wave 64
+// consecutive sites, and the wave walks g with (best lnL, index) in registers:
+//   L   = sum_s freq[s] * x[(g*n + i)*20 + s]   root_lnl_psr_prot_kernel's statement
+//   cnt = sum_{j < nsc} (scalers[j*stride + g*n + i] != 0)
+//   lnl = log(L) + (double)cnt * log(2^-32)     one multiply, one add
+// The 64 rows of segment g (base x + g*n*20: n * 20 values are whole 16-B
+// chunks, so every segment is 16-B aligned) reach the lanes through the wave's
+// own LDS tile, as the edge sums' rows do: coalesced 16-B non-temporal loads,
+// no block barrier in the loop, and candidate g + 1's chunks in flight in
+// registers while the lanes reduce candidate g.  The scaler bytes of candidate
+// g + 1 -- 64 consecutive bytes per wave and row -- are issued behind those
+// chunks, kPsrProtScanRows rows at a time, all loads of a strip before its
+// first use (clamped to the last row, counted only below nsc).  The kernel
+// streams nsc + 20 * sizeof(T) bytes per virtual site.
+// kBest, `first`, all_lnl, out: psr_site_lnl_kernel's rules, word for word --
+// candidate k0 + g replaces (best_lnl, best_idx) iff lnl > best_lnl (ties keep
+// the lower index, a NaN never wins), from (-inf, 0) when `first`; out != NULL
+// (the last pass): out = sum_i wgt_i * best_lnl[i] through lnl_finish.
+constexpr int kPsrProtScanRows = 8;
+
+__device__ __forceinline__ int psr_prot_scaler_count(const uint8_t *__restrict__ scalers, int nsc, int64_t stride,
+                                                     int64_t vs) {
+  int cnt = 0;
+  for (int j0 = 0; j0 < nsc; j0 += kPsrProtScanRows) {
+    uint8_t b[kPsrProtScanRows];
+#pragma unroll
+    for (int u = 0; u < kPsrProtScanRows; u++) {
+      const int j = j0 + u < nsc ? j0 + u : nsc - 1;
+      b[u] = scalers[(int64_t)j * stride + vs];
+    }
+#pragma unroll
+    for (int u = 0; u < kPsrProtScanRows; u++) cnt += (j0 + u < nsc && b[u] != 0) ? 1 : 0;
+  }
+  return cnt;
+}
+
+template <typename T, bool kBest>
+__global__ void __launch_bounds__(kBlock)
+psr_site_lnl_prot_kernel(const T *__restrict__ x, int64_t n, int G, const double *__restrict__ freq,
+                         const uint8_t *__restrict__ scalers, int nsc, int64_t stride, int k0, int first,
+                         double *__restrict__ all_lnl, double *best_lnl, int32_t *best_idx,
+                         const int32_t *__restrict__ wgt, double *partials, unsigned long long *ticket,
+                         double *out) {
+  constexpr int S = 20;
+  using PT = PsrProtTile<T>;
+  using V = typename PT::V;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  __shared__ V tiles[kWavesPerBlock * PT::kChunks];
+  V *const tile = tiles + wave * PT::kChunks;
+  const int64_t seg = n * S;  // values of a segment
+  const int64_t step = (int64_t)gridDim.x * kBlock;
+  const int64_t nlast = n - 1;
+  double acc = 0.0;
+  for (int64_t wbase = (int64_t)blockIdx.x * kBlock + wave * 64; wbase < n; wbase += step) {  // wave-uniform
+    const int64_t site = wbase + lane;
+    const bool in = site < n;
+    const int64_t ld = in ? site : nlast;
+    double bl = -__builtin_inf();
+    int bi = 0;
+    if constexpr (kBest) {
+      if (!first) {
+        bl = best_lnl[ld];
+        bi = best_idx[ld];
+      }
+    }
+    V pf[PT::kChunksPerSite];
+    psr_prot_tile_fetch<T>(x, wbase, n, lane, pf);
+    int cnt_next = psr_prot_scaler_count(scalers, nsc, stride, ld);
+    for (int g = 0; g < G; g++) {
+      const int cnt = cnt_next;
+      psr_prot_tile_put<T>(pf, lane, tile);
+      psr_prot_wave_sync();
+      if (g + 1 < G) {
+        psr_prot_tile_fetch<T>(x + (int64_t)(g + 1) * seg, wbase, n, lane, pf);
+        cnt_next = psr_prot_scaler_count(scalers, nsc, stride, (int64_t)(g + 1) * n + ld);
+      }
+      T v[S];
+      psr_prot_row_read<T>(tile + lane * PT::kStride, v);
+      psr_prot_wave_sync();  // every lane holds its row before the tile is written again
+      double L = 0.0;
+#pragma unroll
+      for (int s = 0; s < S; s++) L += (freq ? freq[s] : 0.05) * (double)v[s];
+      const double corr = (double)cnt * kLogMinLik;
+      const double l = log(L) + corr;
+      if (in) {
+        if (all_lnl) all_lnl[(int64_t)(k0 + g) * n + site] = l;
+        if (kBest && l > bl) {
+          bl = l;
+          bi = k0 + g;
+        }
+      }
+    }
+    if constexpr (kBest) {
+      if (in) {
+        best_lnl[site] = bl;
+        best_idx[site] = bi;
+        if (out) acc += (double)wgt_at(wgt, site, partials) * bl;
+      }
+    }
+  }
+  if constexpr (kBest) {
+    if (out) lnl_finish(acc, partials, ticket, out, nullptr, 0);  // uniform: a kernel argument
+  }
 }
 
 }  // namespace dev

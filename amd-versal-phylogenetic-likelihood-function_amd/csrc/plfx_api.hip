@@ -1399,28 +1399,20 @@ int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const v
       });
 }
 
-// ---- (12) the PSR rate scan ----
+// ---- (12) the PSR rate scan; (12b) the same with a state count ----
+
+// Each entry point of section 12 is its _gen twin with 4 states, as section
+// 11's are.  The _gen entry points: states 4 runs plf_psr.hip's lnL / argmax
+// launchers, states 20 plf_psr_prot.hip's; the checks, the lowering, the
+// tiling launch and the pass loop are shared.
 
 int plfx_site_lnl_psr(plfx_ctx *ctx, int dtype, const void *x, int64_t n, const double *freq,
                       const uint8_t *scalers, int nsc, int64_t stride, double *site_lnl, void *stream) {
-  PLFX_BIND(ctx);
-  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
-  if (n < 0 || !x || !aligned16(x) || !site_lnl || nsc < 0 || (nsc > 0 && !scalers) || stride < n)
-    return fail(ctx, PLFX_ERR_INVALID,
-                "site_lnl_psr: needs n >= 0, a 16-byte aligned x, site_lnl, nsc >= 0 rows (non-NULL when nsc > 0) and "
-                "stride >= n");
-  if (n == 0) return PLFX_OK;
-  hipError_t e = plfx::launch_psr_site_lnl(dtype, x, n, freq, scalers, nsc, stride, site_lnl, ctx->max_blocks,
-                                           pick(stream));
-  if (e != hipSuccess) return hip_fail(ctx, e, "site_lnl_psr launch");
-  return PLFX_OK;
+  return plfx_site_lnl_psr_gen(ctx, dtype, 4, x, n, freq, scalers, nsc, stride, site_lnl, stream);
 }
 
 int plfx_psr_rate_scan_workspace(int dtype, int nops, int ntips, int npmats, int64_t n, int group, size_t *bytes) {
-  plfx::PsrScanLayout lay;
-  if (!bytes || plfx::psr_scan_layout(dtype, nops, ntips, npmats, n, group, &lay) != PLFX_OK) return PLFX_ERR_INVALID;
-  *bytes = lay.end;
-  return PLFX_OK;
+  return plfx_psr_rate_scan_workspace_gen(dtype, 4, nops, ntips, npmats, n, group, bytes);
 }
 
 int plfx_psr_rate_scan(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int nops, const uint8_t *const *tips,
@@ -1428,13 +1420,51 @@ int plfx_psr_rate_scan(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int no
                        const void *tipvec, const double *cand_rates, int ncand, int group, const double *freq,
                        const int32_t *wgt, int64_t n, void *workspace, size_t workspace_bytes, int32_t *best_idx,
                        double *best_lnl, double *all_lnl, double *out_lnl, void *stream) {
+  return plfx_psr_rate_scan_gen(ctx, dtype, 4, ops, nops, tips, nslots, blen, npmats, eigen, EV, tipvec, cand_rates,
+                                ncand, group, freq, wgt, n, workspace, workspace_bytes, best_idx, best_lnl, all_lnl,
+                                out_lnl, stream);
+}
+
+int plfx_site_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                          const uint8_t *scalers, int nsc, int64_t stride, double *site_lnl, void *stream) {
   PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  if (int rc = check_dtype(ctx, dtype); rc != PLFX_OK) return rc;
+  if (n < 0 || !x || !aligned16(x) || !site_lnl || nsc < 0 || (nsc > 0 && !scalers) || stride < n)
+    return fail(ctx, PLFX_ERR_INVALID,
+                "site_lnl_psr: needs n >= 0, a 16-byte aligned x, site_lnl, nsc >= 0 rows (non-NULL when nsc > 0) and "
+                "stride >= n");
+  if (n == 0) return PLFX_OK;
+  const auto launch = states == 4 ? plfx::launch_psr_site_lnl : plfx::launch_psr_site_lnl_prot;
+  hipError_t e = launch(dtype, x, n, freq, scalers, nsc, stride, site_lnl, ctx->max_blocks, pick(stream));
+  if (e != hipSuccess) return hip_fail(ctx, e, "site_lnl_psr launch");
+  return PLFX_OK;
+}
+
+int plfx_psr_rate_scan_workspace_gen(int dtype, int states, int nops, int ntips, int npmats, int64_t n, int group,
+                                     size_t *bytes) {
+  if (int rc = check_psr_states(nullptr, states); rc != PLFX_OK) return rc;
+  plfx::PsrScanLayout lay;
+  if (!bytes || plfx::psr_scan_layout(dtype, nops, ntips, npmats, n, group, &lay, states) != PLFX_OK)
+    return PLFX_ERR_INVALID;
+  *bytes = lay.end;
+  return PLFX_OK;
+}
+
+int plfx_psr_rate_scan_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
+                           const uint8_t *const *tips, int nslots, const double *blen, int npmats,
+                           const double *eigen, const void *EV, const void *tipvec, const double *cand_rates,
+                           int ncand, int group, const double *freq, const int32_t *wgt, int64_t n,
+                           void *workspace, size_t workspace_bytes, int32_t *best_idx, double *best_lnl,
+                           double *all_lnl, double *out_lnl, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
   // lower: every check, the workspace carved, the passes and each pass's launch list, before the first launch
   plfx::PsrScanPlan &pl = ctx->psr_scan;
   const plfx::PsrScanCall call{dtype,  ops,        nops,  tips,  nslots, blen,      npmats,          eigen,
                                EV,     tipvec,     cand_rates,   ncand,  group,     n,               workspace,
                                workspace_bytes,    best_idx,     best_lnl,          all_lnl,         out_lnl,
-                               ctx->psr_fuse};
+                               ctx->psr_fuse,      states};
   std::string err;
   if (int rc = plfx::lower_psr_scan(call, &pl, &err); rc != PLFX_OK) return fail(ctx, rc, "%s", err.c_str());
   hipStream_t s = pick(stream);
@@ -1448,17 +1478,17 @@ int plfx_psr_rate_scan(plfx_ctx *ctx, int dtype, const plfx_trav_op *ops, int no
     if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan tiling launch");
   }
   // passes, one after the other on the stream: each reuses the CLVs, scaler rows and matrices
+  const auto launch_pass = states == 4 ? plfx::launch_psr_scan_pass : plfx::launch_psr_scan_pass_prot;
   for (size_t p = 0; p < pl.passes.size(); p++) {
     const plfx::PsrScanPass &ps = pl.passes[p];
-    hipError_t e = plfx::launch_pmatrix(dtype, true, eigen, 4, cand_rates + ps.k0, ps.gc, blen, 2 * (int64_t)npmats,
-                                        pl.pmats, s);
+    hipError_t e = plfx::launch_pmatrix(dtype, true, eigen, states, cand_rates + ps.k0, ps.gc, blen,
+                                        2 * (int64_t)npmats, pl.pmats, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan pmatrix launch");
-    const plfx::PsrCall pc{dtype, (int64_t)ps.gc * n, ps.gc, EV, pl.cat};
+    const plfx::PsrCall pc{dtype, (int64_t)ps.gc * n, ps.gc, EV, pl.cat, states};
     if (int rc = execute_psr(ctx, ps.tail ? pl.tail : pl.full, pc, nullptr, tipvec, s, w->ws); rc != PLFX_OK) return rc;
     const bool last = p + 1 == pl.passes.size();
-    e = plfx::launch_psr_scan_pass(dtype, pl.root, n, ps.gc, freq, pl.scalers, nops, pl.sc_stride, ps.k0, p == 0,
-                                   all_lnl, best_lnl, best_idx, wgt, w->lnl_partials, w->lnl_ticket,
-                                   last ? out_lnl : nullptr, ctx->max_blocks, s);
+    e = launch_pass(dtype, pl.root, n, ps.gc, freq, pl.scalers, nops, pl.sc_stride, ps.k0, p == 0, all_lnl, best_lnl,
+                    best_idx, wgt, w->lnl_partials, w->lnl_ticket, last ? out_lnl : nullptr, ctx->max_blocks, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan lnl launch");
   }
   return PLFX_OK;

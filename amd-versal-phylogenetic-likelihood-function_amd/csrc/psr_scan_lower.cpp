@@ -40,20 +40,21 @@ void PsrScanPlan::clear() {
   sc_rows.clear();
 }
 
-int psr_scan_layout(int dtype, int nops, int ntips, int npmats, int64_t n, int group, PsrScanLayout *out) {
+int psr_scan_layout(int dtype, int nops, int ntips, int npmats, int64_t n, int group, PsrScanLayout *out,
+                    int states) {
   if ((dtype != PLFX_F32 && dtype != PLFX_F64) || nops < 0 || ntips < 0 || npmats < 0 || n < 0 || group < 1 ||
-      group > PLFX_PSR_MAX_CATS || !out)
+      group > PLFX_PSR_MAX_CATS || !out || (states != 4 && states != 20))
     return PLFX_ERR_INVALID;
-  const size_t es = dtype == PLFX_F32 ? 4 : 8, vn = (size_t)group * (size_t)n;
+  const size_t es = dtype == PLFX_F32 ? 4 : 8, vn = (size_t)group * (size_t)n, S = (size_t)states;
   PsrScanLayout l{};
-  l.clv_stride = up(vn * 4 * es);
+  l.clv_stride = up(vn * S * es);
   l.row = up(vn);
   l.clv0 = 0;
   l.tip0 = l.clv0 + (size_t)nops * l.clv_stride;
   l.sc0 = l.tip0 + (size_t)ntips * l.row;
   l.cat0 = l.sc0 + (size_t)nops * l.row;
   l.pm0 = l.cat0 + l.row;
-  l.end = l.pm0 + up((size_t)2 * (size_t)npmats * (size_t)group * 16 * es);
+  l.end = l.pm0 + up((size_t)2 * (size_t)npmats * (size_t)group * S * S * es);
   *out = l;
   return PLFX_OK;
 }
@@ -62,6 +63,7 @@ int lower_psr_scan(const PsrScanCall &c, PsrScanPlan *out, std::string *err) {
   out->clear();
   const int inv = PLFX_ERR_INVALID;
   if (c.dtype != PLFX_F32 && c.dtype != PLFX_F64) return refuse(out, err, inv, "bad dtype");
+  if (c.states != 4 && c.states != 20) return refuse(out, err, inv, "states must be 4 or 20");
   if (c.n < 0) return refuse(out, err, inv, "n < 0");
   if (c.nops < 1 || !c.ops) return refuse(out, err, inv, "needs nops >= 1 ops");
   if (c.ncand < 1 || c.ncand > PLFX_PSR_SCAN_MAX_RATES)
@@ -77,8 +79,10 @@ int lower_psr_scan(const PsrScanCall &c, PsrScanPlan *out, std::string *err) {
   if (c.tips)
     for (int s = 0; s < c.nslots; s++) mask.push_back(c.tips[s] != nullptr);
   std::string perr;
-  if (plan_traversal(c.ops, c.nops, c.nslots, c.npmats, mask.empty() ? nullptr : mask.data(), 4,
-                     std::min(std::max(c.fuse, 0), 1), &out->trav, &perr) != PLFX_OK)
+  // 20 states: no level pair is built, whatever the context's switch says
+  const int fuse = c.states == 4 ? std::min(std::max(c.fuse, 0), 1) : 0;
+  if (plan_traversal(c.ops, c.nops, c.nslots, c.npmats, mask.empty() ? nullptr : mask.data(), c.states, fuse,
+                     &out->trav, &perr) != PLFX_OK)
     return refuse(out, err, inv, perr.c_str());
   // every slot that is read holds a coded tip or what an earlier op wrote
   std::vector<int> first_write((size_t)c.nslots, -1);
@@ -95,7 +99,7 @@ int lower_psr_scan(const PsrScanCall &c, PsrScanPlan *out, std::string *err) {
   int ntips = 0;
   for (const unsigned char m : mask) ntips += m;
   PsrScanLayout lay{};
-  if (psr_scan_layout(c.dtype, c.nops, ntips, c.npmats, c.n, c.group, &lay) != PLFX_OK)
+  if (psr_scan_layout(c.dtype, c.nops, ntips, c.npmats, c.n, c.group, &lay, c.states) != PLFX_OK)
     return refuse(out, err, inv, "bad sizes");
   if (!c.workspace || (reinterpret_cast<uintptr_t>(c.workspace) % kPsrScanAlign) != 0)
     return refuse(out, err, inv, "the workspace must be non-NULL and 256-byte aligned");
@@ -133,11 +137,11 @@ int lower_psr_scan(const PsrScanCall &c, PsrScanPlan *out, std::string *err) {
   const TravArrays arr{c.ops, c.nops, out->clv.data(), out->wtips.data(), out->pmats, out->sc_rows.data(), nullptr};
   std::string lerr;
   if (c.ncand >= c.group &&
-      lower_psr_traversal(out->trav, arr, PsrCall{c.dtype, (int64_t)c.group * c.n, c.group, c.EV, out->cat},
+      lower_psr_traversal(out->trav, arr, PsrCall{c.dtype, (int64_t)c.group * c.n, c.group, c.EV, out->cat, c.states},
                           &out->full, &lerr) != PLFX_OK)
     return refuse(out, err, inv, lerr.c_str());
   if (tail_gc &&
-      lower_psr_traversal(out->trav, arr, PsrCall{c.dtype, (int64_t)tail_gc * c.n, tail_gc, c.EV, out->cat},
+      lower_psr_traversal(out->trav, arr, PsrCall{c.dtype, (int64_t)tail_gc * c.n, tail_gc, c.EV, out->cat, c.states},
                           &out->tail, &lerr) != PLFX_OK)
     return refuse(out, err, inv, lerr.c_str());
   return PLFX_OK;

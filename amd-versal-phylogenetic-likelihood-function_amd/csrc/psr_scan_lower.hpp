@@ -18,20 +18,22 @@ namespace plfx {
 constexpr size_t kPsrScanAlign = 256;  // of the workspace and of every array carved from it
 
 // Offsets into the workspace, in bytes.  Every array starts on a multiple of
-// kPsrScanAlign: CLV k at clv0 + k * clv_stride (group * n * 4 values), tip
-// array k at tip0 + k * row (group * n bytes), scaler row j at sc0 + j * row,
-// the category bytes at cat0, the matrices at pm0 (2 * npmats * group * 16
-// values); end: the size plfx_psr_rate_scan_workspace reports.
+// kPsrScanAlign: CLV k at clv0 + k * clv_stride (group * n * states values),
+// tip array k at tip0 + k * row (group * n bytes), scaler row j at sc0 + j *
+// row, the category bytes at cat0, the matrices at pm0 (2 * npmats * group *
+// states^2 values); end: the size plfx_psr_rate_scan_workspace_gen reports.
 struct PsrScanLayout {
   size_t clv0, clv_stride, tip0, row, sc0, cat0, pm0, end;
 };
 
-// PLFX_ERR_INVALID for a bad dtype, a negative count or n, or a group outside
-// 1..PLFX_PSR_MAX_CATS.
-int psr_scan_layout(int dtype, int nops, int ntips, int npmats, int64_t n, int group, PsrScanLayout *out);
+// PLFX_ERR_INVALID for a bad dtype, a negative count or n, a group outside
+// 1..PLFX_PSR_MAX_CATS or states other than 4 (plfx.h section 12) and 20 (12b).
+int psr_scan_layout(int dtype, int nops, int ntips, int npmats, int64_t n, int group, PsrScanLayout *out,
+                    int states = 4);
 
 // The arguments of the call, as plfx.h names them; fuse: the context's PSR
-// level-pair switch (PLFX_FUSE).
+// level-pair switch (PLFX_FUSE), which 20 states ignore (the planner is given
+// 0: there is no protein level pair); states: 4 or 20, checked by the caller.
 struct PsrScanCall {
   int dtype;
   const plfx_trav_op *ops;
@@ -50,11 +52,12 @@ struct PsrScanCall {
   int32_t *best_idx;
   double *best_lnl, *all_lnl, *out_lnl;
   int fuse;
+  int states = 4;
 };
 
 // Candidates [k0, k0 + gc) in one traversal of gc * n virtual sites with gc
 // categories; tail: gc < group, the pass runs the `tail` launch list (its
-// matrices are gc * 16 values apart) on prefixes of every array.
+// matrices are gc * states^2 values apart) on prefixes of every array.
 struct PsrScanPass {
   int k0, gc;
   bool tail;

@@ -62,6 +62,7 @@ EXPORTS = (
     "plfx_plf_psr_dev_gen", "plfx_traverse_psr_gen", "plfx_root_lnl_psr_gen", "plfx_psr_site_order",
     "plfx_edge_sumtable_psr_gen", "plfx_edge_sumtable_psr_batch_gen", "plfx_edge_derivatives_psr_gen",
     "plfx_edge_optimize_psr_gen", "plfx_edge_optimize_psr_dev_gen",
+    "plfx_site_lnl_psr_gen", "plfx_psr_rate_scan_gen", "plfx_psr_rate_scan_workspace_gen",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -205,10 +206,14 @@ def load():
             ("plfx_edge_optimize_psr_dev", [pvp, i32, i64, vp, vp, i32, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp])):
         getattr(L, name).argtypes = [vp, i32] + args
         getattr(L, name + "_gen").argtypes = [vp, i32, i32] + args
-    L.plfx_site_lnl_psr.argtypes = [vp, i32, vp, i64, vp, vp, i32, i64, vp, vp]
-    L.plfx_psr_rate_scan.argtypes = [vp, i32, C.POINTER(TravOp), i32, C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, i32,
-                                     i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    L.plfx_psr_rate_scan_workspace.argtypes = [i32, i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)]
+    # the rate scan (section 12) and its _gen twins (12b): states after dtype
+    for name, head, args in (
+            ("plfx_site_lnl_psr", [vp, i32], [vp, i64, vp, vp, i32, i64, vp, vp]),
+            ("plfx_psr_rate_scan", [vp, i32], [top, i32, pvp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp,
+                                               C.c_size_t, vp, vp, vp, vp, vp]),
+            ("plfx_psr_rate_scan_workspace", [i32], [i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)])):
+        getattr(L, name).argtypes = head + args
+        getattr(L, name + "_gen").argtypes = head + [i32] + args
     L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
     L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
     _lib = L
@@ -959,13 +964,22 @@ class Context:
         + (number of rows j < nsc with scalers[j*stride + i] != 0) * log(2^-32).
         scalers: one uint8 device tensor holding the nsc rows (2-D: nsc and
         stride default to its shape; 1-D: pass both), or None for nsc = 0."""
+        self._site_lnl_psr(False, states, x, n, site_lnl, freq, scalers, nsc, stride, stream)
+
+    def site_lnl_psr_gen(self, states, x, n, site_lnl, freq=None, scalers=None, nsc=None, stride=None, stream=None):
+        """site_lnl_psr() with a state count (plfx.h section 12b): states 4 is
+        site_lnl_psr() itself; with states 20 x holds 20*n values and freq 20
+        (None = 1/20 each)."""
+        self._site_lnl_psr(True, states, x, n, site_lnl, freq, scalers, nsc, stride, stream)
+
+    def _site_lnl_psr(self, gen, states, x, n, site_lnl, freq, scalers, nsc, stride, stream):
         import torch
 
-        self._psr_states(False, states)
+        S = self._psr_states(gen, states)
         n = int(n)
-        _tensor(x, "x", (torch.float32, torch.float64), 4 * n)
+        _tensor(x, "x", (torch.float32, torch.float64), S * n)
         _tensor(site_lnl, "site_lnl", torch.float64, n)
-        _tensor(freq, "freq", torch.float64, 4, optional=True)
+        _tensor(freq, "freq", torch.float64, S, optional=True)
         if scalers is None:
             nsc, stride = (0 if nsc is None else int(nsc)), (n if stride is None else int(stride))
         else:
@@ -975,9 +989,8 @@ class Context:
                 raise PlfxError(ERR_INVALID, "scalers must be 2-D (nsc x stride), or pass nsc and stride")
             nsc, stride = int(nsc), int(stride)
             _tensor(scalers, "scalers", torch.uint8, max(nsc - 1, 0) * max(stride, 0) + n if nsc > 0 else 0)
-        self._check(self._L.plfx_site_lnl_psr(
-            self.h, F32 if x.dtype == torch.float32 else F64, _ptr(x), n, _ptr(freq), _ptr(scalers), nsc, stride,
-            _ptr(site_lnl), self._sh(stream)))
+        self._call("plfx_site_lnl_psr", x.dtype, S, True, gen, _ptr(x), n, _ptr(freq), _ptr(scalers), nsc, stride,
+                   _ptr(site_lnl), self._sh(stream))
 
     def psr_rate_scan(self, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx, best_lnl,
                       group=PSR_MAX_CATS, freq=None, wgt=None, all_lnl=None, out_lnl=None, states=4, stream=None):
@@ -993,9 +1006,25 @@ class Context:
         (int32[n]), best_lnl (float64[n]), all_lnl (float64[ncand*n], optional)
         and out_lnl (float64[1], optional) are written.  group: candidates per
         traversal (sizes the workspace; the outputs do not depend on it)."""
+        self._psr_rate_scan(False, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
+                            best_lnl, group, freq, wgt, all_lnl, out_lnl, stream)
+
+    def psr_rate_scan_gen(self, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
+                          best_lnl, group=PSR_MAX_CATS, freq=None, wgt=None, all_lnl=None, out_lnl=None, stream=None):
+        """psr_rate_scan() with a state count (plfx.h section 12b): states 4 is
+        psr_rate_scan() itself.  With states 20 the tips hold protein codes,
+        eigen is what pmatrix(states=20) takes, EV holds 400 values, tipvec is
+        the PROT_CODES x 20 eigen-convention table, freq 20 root weights, and
+        the workspace is psr_rate_scan_workspace_gen(dtype, 20, ...) bytes --
+        its CLVs are five times the DNA size, so `group` is what sizes it."""
+        self._psr_rate_scan(True, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
+                            best_lnl, group, freq, wgt, all_lnl, out_lnl, stream)
+
+    def _psr_rate_scan(self, gen, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
+                       best_lnl, group, freq, wgt, all_lnl, out_lnl, stream):
         import torch
 
-        self._psr_states(False, states)
+        S = self._psr_states(gen, states)
         n, group = int(n), int(group)
         dt = EV.dtype
         if dt not in (torch.float32, torch.float64):
@@ -1008,10 +1037,10 @@ class Context:
         if blen.numel() % 2:
             raise PlfxError(ERR_INVALID, "blen must hold whole (left, right) pairs")
         npmats, ncand = blen.numel() // 2, 0 if cand_rates is None else cand_rates.numel()
-        _tensor(eigen, "eigen", torch.float64, 4 + 2 * 16)
-        _tensor(EV, "EV", dt, 16)
+        _tensor(eigen, "eigen", torch.float64, S + 2 * S * S)
+        _tensor(EV, "EV", dt, S * S)
         _tensor(cand_rates, "cand_rates", torch.float64, 0)
-        _tensor(freq, "freq", torch.float64, 4, optional=True)
+        _tensor(freq, "freq", torch.float64, S, optional=True)
         _check_aux(n, wgt, None, None)
         _tensor(workspace, "workspace", torch.uint8, 0)
         _tensor(best_idx, "best_idx", torch.int32, n)
@@ -1020,11 +1049,10 @@ class Context:
         _tensor(out_lnl, "out_lnl", torch.float64, 1, optional=True)
         top = (TravOp * max(1, nops))(*[TravOp(*map(int, r)) for r in ops])
         tp = (C.c_void_p * max(1, nslots))(*map(_ptr, tips))
-        self._check(self._L.plfx_psr_rate_scan(
-            self.h, F32 if dt == torch.float32 else F64, top, nops, tp, nslots, _ptr(blen), npmats, _ptr(eigen),
-            _ptr(EV), self._tipvec(tipvec, dt), _ptr(cand_rates), ncand, group, _ptr(freq), _ptr(wgt), n,
-            _ptr(workspace), workspace.numel(), _ptr(best_idx), _ptr(best_lnl), _ptr(all_lnl), _ptr(out_lnl),
-            self._sh(stream)))
+        self._call("plfx_psr_rate_scan", dt, S, True, gen, top, nops, tp, nslots, _ptr(blen), npmats, _ptr(eigen),
+                   _ptr(EV), self._tipvec(tipvec, dt, S), _ptr(cand_rates), ncand, group, _ptr(freq), _ptr(wgt), n,
+                   _ptr(workspace), workspace.numel(), _ptr(best_idx), _ptr(best_lnl), _ptr(all_lnl), _ptr(out_lnl),
+                   self._sh(stream))
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):
@@ -1180,17 +1208,32 @@ def gamma_rates(alpha, ncat=4, median=False):
     return out
 
 
-def psr_rate_scan_workspace(dtype, nops, ntips, npmats, n, group=PSR_MAX_CATS):
-    """Bytes of the workspace psr_rate_scan() needs (plfx.h section 12).  dtype:
-    F32 / F64, a numpy dtype or a torch dtype; ntips: the coded tips."""
+def _scan_dtype(dtype):
     if not isinstance(dtype, int):
         name = str(dtype).replace("torch.", "")
         if name not in ("float32", "float64"):
             name = np.dtype(dtype).name
         dtype = {"float32": F32, "float64": F64}.get(name, -1)
+    return int(dtype)
+
+
+def psr_rate_scan_workspace(dtype, nops, ntips, npmats, n, group=PSR_MAX_CATS):
+    """Bytes of the workspace psr_rate_scan() needs (plfx.h section 12).  dtype:
+    F32 / F64, a numpy dtype or a torch dtype; ntips: the coded tips."""
     out = C.c_size_t(0)
-    _host_check(load().plfx_psr_rate_scan_workspace(int(dtype), int(nops), int(ntips), int(npmats), int(n),
+    _host_check(load().plfx_psr_rate_scan_workspace(_scan_dtype(dtype), int(nops), int(ntips), int(npmats), int(n),
                                                     int(group), C.byref(out)), "psr_rate_scan_workspace")
+    return int(out.value)
+
+
+def psr_rate_scan_workspace_gen(dtype, states, nops, ntips, npmats, n, group=PSR_MAX_CATS):
+    """psr_rate_scan_workspace() with a state count (plfx.h section 12b): what
+    psr_rate_scan_gen(states, ...) needs.  With states 20 the CLVs are five
+    times the DNA size; `group` is what sizes the workspace."""
+    out = C.c_size_t(0)
+    _host_check(load().plfx_psr_rate_scan_workspace_gen(_scan_dtype(dtype), int(states), int(nops), int(ntips),
+                                                        int(npmats), int(n), int(group), C.byref(out)),
+                "psr_rate_scan_workspace_gen")
     return int(out.value)
 
 

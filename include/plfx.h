@@ -782,7 +782,8 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
  * section (11) itself (the same kernels, the same bits), states == 20 is the
  * protein path described here, any other value PLFX_ERR_UNSUPPORTED.  The
  * branch-length half (the protein versions of plfx_edge_*_psr) is section
- * (11c); the protein version of section 12's rate scan does not exist yet.
+ * (11c), the rate scan section (12b); an FMA or matrix-core form of the
+ * protein rate scan does not exist yet.
  * With 20 states a PSR CLV is x[site*20 + state] -- n * 20 values of dtype
  * (f32 or f64), a quarter of the Gamma protein layout, base 16-byte aligned;
  *   left, right: ncat * 400 values [c][k][l] -- what plfx_pmatrix(states = 20)
@@ -1012,6 +1013,63 @@ int plfx_psr_rate_scan_workspace(int dtype, int nops, int ntips, int npmats, int
 int plfx_psr_categorize(const double *cand_rates, int ncand, const int32_t *best_idx, const int32_t *wgt,
                         int64_t n, int max_cats, uint8_t *rate_cat, double *cat_rates, int *ncat,
                         double *scale);
+
+/* ---- (12b) the rate scan with a state count (PROTCAT; extension) -----------
+ * The three entry points below are their section-(12) namesakes with a
+ * `states` argument after dtype (the workspace query has no ctx: dtype comes
+ * first there, then states), as sections (11b) and (11c) do it: states == 4
+ * is section (12) itself -- one
+ * code path, the same launchers, the same bits --, states == 20 the protein
+ * path described here, any other value PLFX_ERR_UNSUPPORTED.  What the scan
+ * produces feeds plfx_psr_categorize, plfx_psr_site_order and then every call
+ * of sections (11b) and (11c). */
+
+/* plfx_site_lnl_psr with a state count: x holds n * states values of dtype
+ * (16-byte aligned), freq `states` doubles or NULL (1/states each);
+ *   L_i = sum_s freq[s] * x[i][s]      from +0.0, ascending s, in f64
+ *   site_lnl[i] = log(L_i) + cnt_i * log(2^-32)        one multiply, one add
+ * with cnt_i over the nsc scaler rows as in section (12).  With nsc == 0 it
+ * gives plfx_root_lnl_psr_gen's site_lnl bit for bit.  The checks and the
+ * n == 0 rule are plfx_site_lnl_psr's. */
+int plfx_site_lnl_psr_gen(plfx_ctx *ctx, int dtype, int states, const void *x, int64_t n, const double *freq,
+                          const uint8_t *scalers, int nsc, int64_t stride, double *site_lnl, void *stream);
+
+/* plfx_psr_rate_scan with a state count.  With states == 20: eigen is what
+ * plfx_pmatrix(states = 20) takes, EV holds 400 values of dtype, tipvec
+ * (required) is a 24 x 20 table of dtype in the eigen convention, freq holds
+ * 20 root weights or is NULL (1/20 each), and the tips are protein codes (row
+ * min(code, 23)).  The outputs, the tie and NaN rules (strict >: ties keep the
+ * lower k, a NaN never wins, all NaN gives best_idx 0 and best_lnl -inf) and
+ * out_lnl's fixed-order reduction are section (12)'s.  The mechanism too: the
+ * codes and category bytes tiled once, then per pass plfx_pmatrix (EIGEN,
+ * states, ncat = gc), the plfx_traverse_psr_gen launches over gc * n virtual
+ * sites -- which arrive sorted by category by construction, the order the
+ * protein node kernel is fast in; with 20 states no level pair is fused,
+ * whatever PLFX_FUSE says -- and one kernel for the per-site lnL and the
+ * running best.  Row k of all_lnl is bit for bit what plfx_traverse_psr_gen
+ * (rate_cat all k) followed by plfx_site_lnl_psr_gen gives, and every output
+ * has the same bits for every group.  workspace: at least
+ * plfx_psr_rate_scan_workspace_gen(dtype, states, ...) bytes, 256-byte
+ * aligned: one sized for 4 states is refused for 20.  Asynchronous, allocates
+ * nothing, capture-safe; every check runs before the first launch, with
+ * section (12)'s codes. */
+int plfx_psr_rate_scan_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_op *ops, int nops,
+                           const uint8_t *const *tips, int nslots, const double *blen, int npmats,
+                           const double *eigen, const void *EV, const void *tipvec, const double *cand_rates,
+                           int ncand, int group, const double *freq, const int32_t *wgt, int64_t n,
+                           void *workspace, size_t workspace_bytes, int32_t *best_idx, double *best_lnl,
+                           double *all_lnl, double *out_lnl, void *stream);
+
+/* Host only.  *bytes = section (12)'s formula with `states` in place of 4 and
+ * states^2 in place of 16, each array rounded up to 256 bytes: nops CLVs of
+ * group*n*states values of dtype, ntips + nops + 1 rows of group*n bytes (the
+ * code arrays, the scaler rows, the category bytes), 2*npmats*group*states^2
+ * matrix values.  With 20 states the CLVs are five times the DNA size and
+ * they are nearly all of it: `group` is what sizes the workspace -- choose it
+ * to fit, the results do not depend on it.  PLFX_ERR_UNSUPPORTED for states
+ * other than 4 and 20; PLFX_ERR_INVALID as plfx_psr_rate_scan_workspace. */
+int plfx_psr_rate_scan_workspace_gen(int dtype, int states, int nops, int ntips, int npmats, int64_t n, int group,
+                                     size_t *bytes);
 
 #ifdef __cplusplus
 } /* extern "C" */
