@@ -175,6 +175,13 @@ hipError_t launch_root_lnl_psr_prot(int dtype, const void *x, int64_t n, const d
                                     const int64_t *scaler_sums, int nsums, double *partials,
                                     unsigned long long *ticket, double *out, double *site_lnl, int max_blocks,
                                     hipStream_t s);
+// The same node in FMA mode on the f64 matrix cores (plfx.h section 11d;
+// plf_psr_prot_mfma.hpp; defined in plf_psr_prot_mfma.hip =
+// libplfx_psr_prot_mfma.so, which libplfx.so links): f64 only, the arguments
+// of launch_plf_psr_prot without the dtype.
+hipError_t launch_plf_psr_prot_mfma(int tips, const NodeDescH *nodes, int count, const void *EV,
+                                    const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n,
+                                    const void *tipvec, unsigned long long *ws, int max_blocks, hipStream_t s);
 // The branch-length half (plfx.h section 11c): launch_edge_sumtable_psr,
 // _psr_batch, launch_edge_derivatives_psr and launch_edge_optimize_psr for
 // tables of n * 20 values, tipvec 24 x 20 values; n >= 1 for the sum tables.

@@ -519,10 +519,14 @@ int execute_psr(plfx_ctx *ctx, const plfx::PsrLaunchList &l, const plfx::PsrCall
   for (const plfx::PsrLaunch &it : l.items) {
     const bool triples = it.kind == plfx::kPsrTriples;
     if (c.states == 20) {  // section 11b: node batches only (the lowering emits no level pair)
-      const hipError_t e = triples ? hipErrorInvalidValue
-                                   : plfx::launch_plf_psr_prot(c.dtype, it.tips, &l.nodes[it.first], it.count, c.EV,
-                                                               c.rate_cat, c.ncat, wgt, c.n, tipvec, ws,
-                                                               ctx->max_blocks, s);
+      // section 11d: PLFX_FMA runs the same list on the matrix-core kernel (f64, checked by the entry point)
+      hipError_t e = hipErrorInvalidValue;
+      if (!triples)
+        e = (c.flags & PLFX_FMA)
+                ? plfx::launch_plf_psr_prot_mfma(it.tips, &l.nodes[it.first], it.count, c.EV, c.rate_cat, c.ncat, wgt,
+                                                 c.n, tipvec, ws, ctx->max_blocks, s)
+                : plfx::launch_plf_psr_prot(c.dtype, it.tips, &l.nodes[it.first], it.count, c.EV, c.rate_cat, c.ncat,
+                                            wgt, c.n, tipvec, ws, ctx->max_blocks, s);
       if (e != hipSuccess) return hip_fail(ctx, e, "plf_psr protein launch");
       continue;
     }
@@ -703,6 +707,17 @@ int edge_optimize_dev(plfx_ctx *ctx, const char *who, const void *const *sumtabs
 int check_psr_states(plfx_ctx *ctx, int states) {
   if (states != 4 && states != 20)
     return fail(ctx, PLFX_ERR_UNSUPPORTED, "per-site rate categories: states=%d not built (4, 20)", states);
+  return PLFX_OK;
+}
+
+// The flags of the plfx_*_psr_ex entry points (plfx.h section 11d), after the
+// states check: what the call runs with -- 0 for 4 states ("DNA is always
+// exact") -- into *mode.  who: the entry point, for the message.
+int check_psr_flags(plfx_ctx *ctx, const char *who, int dtype, int states, int flags, int *mode) {
+  if (flags & ~PLFX_FMA) return fail(ctx, PLFX_ERR_INVALID, "%s: bad flags %d", who, flags);
+  *mode = states == 20 ? flags : 0;
+  if (*mode && dtype == PLFX_F32)
+    return fail(ctx, PLFX_ERR_UNSUPPORTED, "%s: PLFX_FMA with 20 states is built for f64 only", who);
   return PLFX_OK;
 }
 
@@ -1249,11 +1264,21 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
 int plfx_plf_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const plfx_psr_node *nodes, int count,
                          const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
                          const void *tipvec, void *stream) {
+  return plfx_plf_psr_dev_ex(ctx, dtype, states, 0, nodes, count, EV, n, rate_cat, ncat, wgt, tipvec, stream);
+}
+
+// ---- (11d) the _ex entry points: the _gen calls with flags; flags 0 is the _gen call ----
+
+int plfx_plf_psr_dev_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_psr_node *nodes, int count,
+                        const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                        const void *tipvec, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  int mode;
+  if (int rc = check_psr_flags(ctx, "plf_psr_dev_ex", dtype, states, flags, &mode); rc != PLFX_OK) return rc;
   static_assert(PLFX_PSR_MAX_CATS <= 256, "a category is one byte");
   std::string err;
-  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states};
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states, mode};
   if (plfx::lower_psr(call, nodes, count, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
   hipStream_t s = pick(stream);
@@ -1267,8 +1292,18 @@ int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_
                           int npmats, const void *EV, int64_t n, const uint8_t *rate_cat, int ncat,
                           const int32_t *wgt, uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec,
                           void *stream) {
+  return plfx_traverse_psr_ex(ctx, dtype, states, 0, ops, nops, clv, tips, nslots, pmats, npmats, EV, n, rate_cat,
+                              ncat, wgt, scalers, scaler_sums, tipvec, stream);
+}
+
+int plfx_traverse_psr_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                         void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                         uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  int mode;
+  if (int rc = check_psr_flags(ctx, "traverse_psr_ex", dtype, states, flags, &mode); rc != PLFX_OK) return rc;
   for (int &c : ctx->sched) c = 0;
   if (nops < 0 || (nops > 0 && (!ops || !clv))) return fail(ctx, PLFX_ERR_INVALID, "bad traverse_psr arguments");
   // level pairs alone: the deeper passes of entries 0..3 of the schedule are not built for PSR;
@@ -1279,7 +1314,7 @@ int plfx_traverse_psr_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav_
   // lower: the call, every op and every level pair checked, every descriptor
   // filled, before the first launch
   const plfx::TravArrays arrays{ops, nops, clv, tips, pmats, scalers, scaler_sums};
-  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states};
+  const plfx::PsrCall call{dtype, n, ncat, EV, rate_cat, states, mode};
   std::string err;
   if (plfx::lower_psr_traversal(plan, arrays, call, &ctx->psr_lowered, &err) != PLFX_OK)
     return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
@@ -1457,14 +1492,27 @@ int plfx_psr_rate_scan_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav
                            int ncand, int group, const double *freq, const int32_t *wgt, int64_t n,
                            void *workspace, size_t workspace_bytes, int32_t *best_idx, double *best_lnl,
                            double *all_lnl, double *out_lnl, void *stream) {
+  return plfx_psr_rate_scan_ex(ctx, dtype, states, 0, ops, nops, tips, nslots, blen, npmats, eigen, EV, tipvec,
+                               cand_rates, ncand, group, freq, wgt, n, workspace, workspace_bytes, best_idx, best_lnl,
+                               all_lnl, out_lnl, stream);
+}
+
+int plfx_psr_rate_scan_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                          const uint8_t *const *tips, int nslots, const double *blen, int npmats,
+                          const double *eigen, const void *EV, const void *tipvec, const double *cand_rates,
+                          int ncand, int group, const double *freq, const int32_t *wgt, int64_t n, void *workspace,
+                          size_t workspace_bytes, int32_t *best_idx, double *best_lnl, double *all_lnl,
+                          double *out_lnl, void *stream) {
   PLFX_BIND(ctx);
   if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  int mode;
+  if (int rc = check_psr_flags(ctx, "psr_rate_scan_ex", dtype, states, flags, &mode); rc != PLFX_OK) return rc;
   // lower: every check, the workspace carved, the passes and each pass's launch list, before the first launch
   plfx::PsrScanPlan &pl = ctx->psr_scan;
   const plfx::PsrScanCall call{dtype,  ops,        nops,  tips,  nslots, blen,      npmats,          eigen,
                                EV,     tipvec,     cand_rates,   ncand,  group,     n,               workspace,
                                workspace_bytes,    best_idx,     best_lnl,          all_lnl,         out_lnl,
-                               ctx->psr_fuse,      states};
+                               ctx->psr_fuse,      states,       mode};
   std::string err;
   if (int rc = plfx::lower_psr_scan(call, &pl, &err); rc != PLFX_OK) return fail(ctx, rc, "%s", err.c_str());
   hipStream_t s = pick(stream);
@@ -1484,7 +1532,7 @@ int plfx_psr_rate_scan_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav
     hipError_t e = plfx::launch_pmatrix(dtype, true, eigen, states, cand_rates + ps.k0, ps.gc, blen,
                                         2 * (int64_t)npmats, pl.pmats, s);
     if (e != hipSuccess) return hip_fail(ctx, e, "psr_rate_scan pmatrix launch");
-    const plfx::PsrCall pc{dtype, (int64_t)ps.gc * n, ps.gc, EV, pl.cat, states};
+    const plfx::PsrCall pc{dtype, (int64_t)ps.gc * n, ps.gc, EV, pl.cat, states, call.flags};
     if (int rc = execute_psr(ctx, ps.tail ? pl.tail : pl.full, pc, nullptr, tipvec, s, w->ws); rc != PLFX_OK) return rc;
     const bool last = p + 1 == pl.passes.size();
     e = launch_pass(dtype, pl.root, n, ps.gc, freq, pl.scalers, nops, pl.sc_stride, ps.k0, p == 0, all_lnl, best_lnl,

@@ -18,7 +18,8 @@ namespace plfx {
 
 // What the nodes of a call share.  states: 4 (plfx.h section 11) or 20
 // (section 11b): values per site of a CLV, and states * states per category
-// of a matrix.
+// of a matrix.  flags: 0, or PLFX_FMA (section 11d) -- the lowered list does
+// not depend on it, only the launcher the executor picks for 20 states.
 struct PsrCall {
   int dtype;
   int64_t n;
@@ -26,6 +27,7 @@ struct PsrCall {
   const void *EV;
   const uint8_t *rate_cat;
   int states = 4;
+  int flags = 0;
 };
 
 enum PsrLaunchKind {

@@ -33,7 +33,9 @@ int psr_scan_layout(int dtype, int nops, int ntips, int npmats, int64_t n, int g
 
 // The arguments of the call, as plfx.h names them; fuse: the context's PSR
 // level-pair switch (PLFX_FUSE), which 20 states ignore (the planner is given
-// 0: there is no protein level pair); states: 4 or 20, checked by the caller.
+// 0: there is no protein level pair); states: 4 or 20, checked by the caller;
+// flags: 0 or PLFX_FMA (section 11d), handed to every pass's PsrCall -- the
+// plan does not depend on it.
 struct PsrScanCall {
   int dtype;
   const plfx_trav_op *ops;
@@ -53,6 +55,7 @@ struct PsrScanCall {
   double *best_lnl, *all_lnl, *out_lnl;
   int fuse;
   int states = 4;
+  int flags = 0;
 };
 
 // Candidates [k0, k0 + gc) in one traversal of gc * n virtual sites with gc

@@ -63,6 +63,7 @@ EXPORTS = (
     "plfx_edge_sumtable_psr_gen", "plfx_edge_sumtable_psr_batch_gen", "plfx_edge_derivatives_psr_gen",
     "plfx_edge_optimize_psr_gen", "plfx_edge_optimize_psr_dev_gen",
     "plfx_site_lnl_psr_gen", "plfx_psr_rate_scan_gen", "plfx_psr_rate_scan_workspace_gen",
+    "plfx_plf_psr_dev_ex", "plfx_traverse_psr_ex", "plfx_psr_rate_scan_ex",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -214,6 +215,10 @@ def load():
             ("plfx_psr_rate_scan_workspace", [i32], [i32, i32, i32, i64, i32, C.POINTER(C.c_size_t)])):
         getattr(L, name).argtypes = head + args
         getattr(L, name + "_gen").argtypes = head + [i32] + args
+    # the PROTCAT FMA entries (section 11d): their _gen bases with flags after states
+    for name in ("plfx_plf_psr_dev", "plfx_traverse_psr", "plfx_psr_rate_scan"):
+        base = getattr(L, name + "_gen").argtypes
+        getattr(L, name + "_ex").argtypes = base[:3] + [i32] + base[3:]
     L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
     L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
     _lib = L
@@ -303,12 +308,17 @@ class Context:
         if rc != OK:
             raise PlfxError(rc, self._L.plfx_last_error(self.h).decode(errors="replace"))
 
-    def _call(self, name, dt, states, psr, gen, *args):
+    def _call(self, name, dt, states, psr, gen, *args, flags=None):
         """Call the C entry `name` on tensors of dtype dt.  A Gamma entry takes
         the state count after the dtype; a per-site-rate entry (psr) is
-        `name`, or with gen its _gen twin, which alone takes the state count."""
+        `name`, or with gen its _gen twin, which alone takes the state count;
+        with flags (section 11d) the _gen twin's _ex form, flags after states."""
         import torch
 
+        if flags is not None:
+            fn = getattr(self._L, name + "_ex")
+            self._check(fn(self.h, F32 if dt == torch.float32 else F64, states, int(flags), *args))
+            return
         fn = getattr(self._L, name + ("_gen" if psr and gen else ""))
         self._check(fn(self.h, F32 if dt == torch.float32 else F64, *((states,) if gen or not psr else ()), *args))
 
@@ -782,15 +792,17 @@ class Context:
         left / right hold ncat * 16 values."""
         self._plf_psr(False, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream)
 
-    def plf_psr_gen(self, states, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, stream=None):
+    def plf_psr_gen(self, states, nodes, EV, n, rate_cat, ncat, wgt=None, tipvec=None, stream=None, fma=False):
         """plf_psr() with a state count (plfx.h section 11b): states 4 is
         plf_psr() itself, states 20 the protein node -- CLVs of 20*n values,
         left / right of ncat * 400, EV of 400, uint8 protein codes (PROT_CODES
         rows of 20 in tipvec, None = the default table).  Fast when the sites
-        are sorted by category: see psr_site_order()."""
-        self._plf_psr(True, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream)
+        are sorted by category: see psr_site_order().  fma: PLFX_FMA through
+        plfx_plf_psr_dev_ex (section 11d) -- with 20 states every multiply-add
+        fused on the f64 matrix cores (float64 only); 4 states stay exact."""
+        self._plf_psr(True, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream, FMA if fma else None)
 
-    def _plf_psr(self, gen, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream):
+    def _plf_psr(self, gen, states, nodes, EV, n, rate_cat, ncat, wgt, tipvec, stream, flags=None):
         import torch
 
         S = self._psr_states(gen, states)
@@ -815,7 +827,7 @@ class Context:
             arr[i] = PsrNode(*(_ptr(nd.get(k)) for k in ("tip1", "x1", "tip2", "x2", "x3", "left", "right",
                                                           "scaler", "scaler_sum")))
         self._call("plfx_plf_psr_dev", dt, S, True, gen, arr, len(nodes), _ptr(EV), n, _ptr(rate_cat), ncat,
-                   _ptr(wgt), self._tipvec(tipvec, dt, S), self._sh(stream))
+                   _ptr(wgt), self._tipvec(tipvec, dt, S), self._sh(stream), flags=flags)
 
     def traverse_psr(self, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None, scaler_sums=None,
                      stream=None, tips=None, tipvec=None, states=4):
@@ -831,16 +843,17 @@ class Context:
                            tips, tipvec)
 
     def traverse_psr_gen(self, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt=None, scalers=None,
-                         scaler_sums=None, stream=None, tips=None, tipvec=None):
+                         scaler_sums=None, stream=None, tips=None, tipvec=None, fma=False):
         """traverse_psr() with a state count (plfx.h section 11b).  With
         states 20 a CLV slot holds 20*n values, pmats whole (left, right) pairs
         of ncat * 400 values each, and no level pair is fused whatever
-        PLFX_FUSE says: last_schedule() reports triples 0, unfused = the ops."""
+        PLFX_FUSE says: last_schedule() reports triples 0, unfused = the ops.
+        fma: PLFX_FMA through plfx_traverse_psr_ex, as plf_psr_gen()."""
         self._traverse_psr(True, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt, scalers, scaler_sums, stream,
-                           tips, tipvec)
+                           tips, tipvec, FMA if fma else None)
 
     def _traverse_psr(self, gen, states, ops, clv, pmats, EV, n, rate_cat, ncat, wgt, scalers, scaler_sums, stream,
-                      tips, tipvec):
+                      tips, tipvec, flags=None):
         import torch
 
         S = self._psr_states(gen, states)
@@ -853,7 +866,7 @@ class Context:
         _tensor(rate_cat, "rate_cat", torch.uint8, n)
         self._call("plfx_traverse_psr", dt, S, True, gen, top, nops, slots, tp, nslots, _ptr(pmats), npmats, _ptr(EV),
                    n, _ptr(rate_cat), ncat, _ptr(wgt), sc, _ptr(scaler_sums), self._tipvec(tipvec, dt, S),
-                   self._sh(stream))
+                   self._sh(stream), flags=flags)
 
     def root_lnl_psr(self, x, n, out, freq=None, wgt=None, scaler_sums=None, site_lnl=None, states=4,
                      stream=None):
@@ -1010,18 +1023,21 @@ class Context:
                             best_lnl, group, freq, wgt, all_lnl, out_lnl, stream)
 
     def psr_rate_scan_gen(self, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
-                          best_lnl, group=PSR_MAX_CATS, freq=None, wgt=None, all_lnl=None, out_lnl=None, stream=None):
+                          best_lnl, group=PSR_MAX_CATS, freq=None, wgt=None, all_lnl=None, out_lnl=None, stream=None,
+                          fma=False):
         """psr_rate_scan() with a state count (plfx.h section 12b): states 4 is
         psr_rate_scan() itself.  With states 20 the tips hold protein codes,
         eigen is what pmatrix(states=20) takes, EV holds 400 values, tipvec is
         the PROT_CODES x 20 eigen-convention table, freq 20 root weights, and
         the workspace is psr_rate_scan_workspace_gen(dtype, 20, ...) bytes --
-        its CLVs are five times the DNA size, so `group` is what sizes it."""
+        its CLVs are five times the DNA size, so `group` is what sizes it.
+        fma: PLFX_FMA through plfx_psr_rate_scan_ex: every pass's traversal in
+        FMA mode, as traverse_psr_gen(fma=True)."""
         self._psr_rate_scan(True, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
-                            best_lnl, group, freq, wgt, all_lnl, out_lnl, stream)
+                            best_lnl, group, freq, wgt, all_lnl, out_lnl, stream, FMA if fma else None)
 
     def _psr_rate_scan(self, gen, states, ops, tips, blen, eigen, EV, tipvec, cand_rates, n, workspace, best_idx,
-                       best_lnl, group, freq, wgt, all_lnl, out_lnl, stream):
+                       best_lnl, group, freq, wgt, all_lnl, out_lnl, stream, flags=None):
         import torch
 
         S = self._psr_states(gen, states)
@@ -1052,7 +1068,7 @@ class Context:
         self._call("plfx_psr_rate_scan", dt, S, True, gen, top, nops, tp, nslots, _ptr(blen), npmats, _ptr(eigen),
                    _ptr(EV), self._tipvec(tipvec, dt, S), _ptr(cand_rates), ncand, group, _ptr(freq), _ptr(wgt), n,
                    _ptr(workspace), workspace.numel(), _ptr(best_idx), _ptr(best_lnl), _ptr(all_lnl), _ptr(out_lnl),
-                   self._sh(stream))
+                   self._sh(stream), flags=flags)
 
     # -- (4) scaler reduction ----------------------------------------------
     def scaler_sum(self, scaler, wgt, out_sum, n=None, stream=None):

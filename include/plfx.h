@@ -782,8 +782,9 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
  * section (11) itself (the same kernels, the same bits), states == 20 is the
  * protein path described here, any other value PLFX_ERR_UNSUPPORTED.  The
  * branch-length half (the protein versions of plfx_edge_*_psr) is section
- * (11c), the rate scan section (12b); an FMA or matrix-core form of the
- * protein rate scan does not exist yet.
+ * (11c), the rate scan section (12b), the FMA mode on the f64 matrix cores
+ * section (11d); an f32 FMA form of the protein node and rate scan does not
+ * exist yet.
  * With 20 states a PSR CLV is x[site*20 + state] -- n * 20 values of dtype
  * (f32 or f64), a quarter of the Gamma protein layout, base 16-byte aligned;
  *   left, right: ncat * 400 values [c][k][l] -- what plfx_pmatrix(states = 20)
@@ -791,8 +792,8 @@ int plfx_edge_sumtable_psr_batch(plfx_ctx *ctx, int dtype, const plfx_psr_edge *
  *   rate_cat, the clamp c = min(rate_cat[i], ncat-1) and 1 <= ncat <=
  *             PLFX_PSR_MAX_CATS as in section (11).
  * Node update -- plf()'s loop with one category, run on each category's sites
- * with that category's matrices; no FMA contraction, so exact mode is the
- * only mode:
+ * with that category's matrices; no FMA contraction: the entry points of
+ * this section run exact mode (section (11d) has the fused one):
  *   umpL[k]  = sum_l x1[i][l] * left[c*400 + k*20 + l]    from +0.0, ascending l
  *                                                         (same for right / x2)
  *   x3[i][l] = sum_k (umpL[k] * umpR[k]) * EV[20k + l]    from +0.0, ascending k
@@ -1070,6 +1071,67 @@ int plfx_psr_rate_scan_gen(plfx_ctx *ctx, int dtype, int states, const plfx_trav
  * other than 4 and 20; PLFX_ERR_INVALID as plfx_psr_rate_scan_workspace. */
 int plfx_psr_rate_scan_workspace_gen(int dtype, int states, int nops, int ntips, int npmats, int64_t n, int group,
                                      size_t *bytes);
+
+/* ---- (11d) PROTCAT FMA mode: the protein PSR node on the f64 matrix cores ----
+ * (extension).  The three entry points below are their _gen namesakes of
+ * sections (11b) and (12b) with an `int flags` argument after states, named
+ * like plfx_ctx_create_ex.  flags: 0 or PLFX_FMA; any other bit is
+ * PLFX_ERR_INVALID.  flags == 0 is the _gen call -- one code path, the same
+ * bits.  states == 4 is section (11) / (12) bit for bit whatever the flag
+ * (DNA is always exact).  states == 20 with PLFX_FMA and dtype f32 is
+ * PLFX_ERR_UNSUPPORTED (not built); PLFX_VALU is not a flag of these calls.
+ *
+ * FMA mode for a protein PSR node is plf()'s loop with one category, run on
+ * each category's sites with that category's matrices, every multiply-add
+ * fused, in the order of the Gamma PLFX_FMA mode of section (2b).  With
+ * c = min(rate_cat[i], ncat-1):
+ *   umpL[k]  : u = +0.0; for l = 0..19 ascending: u = fma(x1[i][l], left[c*400 + 20k + l], u)
+ *                                                         (same for right / x2)
+ *   p[k]     = umpL[k] * umpR[k]                          one rounding
+ *   x3[i][l] : a = +0.0; for k = 0..19 ascending: a = fma(p[k], EV[20k + l], a)
+ * The scale rule is section (11b)'s unchanged: all twenty |x3| < 2^-32 strict,
+ * NaN never scales, x 2^32, scaler byte, wgt into the node's sum.  A coded
+ * child is the row min(code, 23) of the 24 x 20 tip table put through the
+ * same arithmetic: bit-identical to the dense call on the expanded child;
+ * there is no (category, code) table.  On random inputs the values differ in
+ * bits from exact mode on about three quarters of the entries and agree to
+ * about 6e-13 relative.
+ *
+ * The kernel (csrc/plf_psr_prot_mfma.hpp) makes the category uniform across a
+ * wave of 64 consecutive sites by looping, as the exact one does: the same
+ * bits for any order of the sites, and section (11b)'s SITE ORDER paragraph
+ * holds -- sort the sites by category.  plfx_root_lnl_psr_gen,
+ * plfx_site_lnl_psr_gen and all of section (11c) do not depend on the mode.
+ *
+ * Every other check, the n == 0 rule, "every check before the first launch, a
+ * refused call enqueues nothing", asynchrony, no allocation and capture safety
+ * are as in the _gen calls. */
+
+/* plfx_plf_psr_dev_gen with flags. */
+int plfx_plf_psr_dev_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_psr_node *nodes, int count,
+                        const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                        const void *tipvec, void *stream);
+
+/* plfx_traverse_psr_gen with flags: the launch list is the exact call's, only
+ * the node kernel differs.  Every CLV, scaler byte and scaler_sums[j] is
+ * bit-identical to the ops run one by one as one-node plfx_plf_psr_dev_ex
+ * calls with the same flags.  There is no level pair for 20 states. */
+int plfx_traverse_psr_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                         void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats, int npmats,
+                         const void *EV, int64_t n, const uint8_t *rate_cat, int ncat, const int32_t *wgt,
+                         uint8_t *const *scalers, int64_t *scaler_sums, const void *tipvec, void *stream);
+
+/* plfx_psr_rate_scan_gen with flags: the same workspace
+ * (plfx_psr_rate_scan_workspace_gen), passes and outputs, every pass's
+ * traversal in the mode of flags.  The same bits for every group; equal bit
+ * for bit to the per-candidate composition plfx_pmatrix + plfx_traverse_psr_ex
+ * (same flags) + plfx_root_lnl_psr_gen / plfx_site_lnl_psr_gen. */
+int plfx_psr_rate_scan_ex(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                          const uint8_t *const *tips, int nslots, const double *blen, int npmats,
+                          const double *eigen, const void *EV, const void *tipvec, const double *cand_rates,
+                          int ncand, int group, const double *freq, const int32_t *wgt, int64_t n, void *workspace,
+                          size_t workspace_bytes, int32_t *best_idx, double *best_lnl, double *all_lnl,
+                          double *out_lnl, void *stream);
 
 #ifdef __cplusplus
 } /* extern "C" */
