@@ -71,6 +71,27 @@ struct TripleDescH {
 };
 constexpr int kMaxTriples = 10;
 
+// A fused sibling pair (plf_psr_branch.hpp BranchPairDesc): op (v, c1, c2)
+// with W(v) dense.  c1 / c2: the children, coded child first (the uint8
+// codes of a coded child); p1 / p2 their matrices; w1 / w2 the outer CLVs
+// (NULL for a coded child: never written), t1 / t2 the tables, ss1 / ss2 the
+// weighted scaler sums of W(c1) / W(c2) (NULL: not wanted).
+struct BranchPairDescH {
+  const void *wv, *c1, *c2;
+  const void *pup, *p1, *p2;
+  void *w1, *w2, *t1, *t2;
+  int64_t *ss1, *ss2;
+};
+constexpr int kMaxPairs = 16;  // 16 * 96 B of descriptors; two ticket regions each
+
+// One op of the counters' pass (plf_psr_branch.hpp BranchScaleDesc): w1 / w2
+// the ops that wrote its children (-1: a tip), up the edge of its parent slot
+// in the op that reads it (-1: the root op).
+struct BranchScaleDescH {
+  int32_t w1, w2, up;
+};
+constexpr int kScaleChunk = 256;  // ops per launch of the counters' kernel: 3 KB of descriptors
+
 // Fused three-level subtrees (plf_dna.hpp SeptetDesc); <= kMaxSeptets per launch.
 struct SeptetDescH {
   const void *g[8];

@@ -164,6 +164,21 @@ hipError_t launch_psr_scan_pass(int dtype, const void *x, int64_t n, int gc, con
 hipError_t launch_psr_tile(const PsrTileDescH *tips, int count, int64_t n, int group, uint8_t *cat, int max_blocks,
                            hipStream_t s);
 
+// All-branch derivatives of a PSR tree (plfx.h section 13; plf_psr_branch.hpp;
+// defined in plf_psr_branch.hip = libplfx_psr_branch.so, which libplfx.so
+// links): DNA.  Pairs: count <= kMaxPairs ops per launch, ws >= 2 * count
+// regions; tips 0 / 1 / 2 = the coded children of each op, coded child first.
+// Counts: one chunk of count <= kScaleChunk ops from `first` -- the subtree
+// sums (outer_pass false; scaler_sums -> sub) or the outer sums and edge_scale
+// (true; wsum, sub -> outer, edge_scale), one block.
+hipError_t launch_psr_branch_pairs(int dtype, int tips, const BranchPairDescH *pairs, int count, const void *EV,
+                                   const uint8_t *rate_cat, int ncat, const int32_t *wgt, int64_t n,
+                                   const void *tipvec, unsigned long long *ws, int max_blocks, hipStream_t s);
+hipError_t launch_psr_branch_counts(bool outer_pass, const BranchScaleDescH *ops, int first, int count,
+                                    const int64_t *scaler_sums, const int64_t *wsum, int64_t *sub, int64_t *outer,
+                                    int64_t *edge_scale, hipStream_t s);
+int psr_branch_sites_per_lane(int dtype);  // the pair kernel's sites per lane and trip (dtype 1 = f64)
+
 // Protein per-site rate categories (plfx.h section 11b; plf_psr_prot.hpp;
 // defined in plf_psr_prot.hip = libplfx_psr_prot.so, which libplfx.so links):
 // CLVs of n * 20 values, every matrix of ncat * 400, tipvec NULL or 24 x 20

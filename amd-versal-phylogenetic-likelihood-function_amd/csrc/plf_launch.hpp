@@ -1,6 +1,7 @@
-// plf_launch.hpp -- host-side helpers shared by the launchers of the six HIP
+// plf_launch.hpp -- host-side helpers shared by the launchers of the HIP
 // translation units (plf_kernels.hip, plf_prot_valu.hip,
-// plf_prot_valu_exact.hip, plf_edge.hip, plf_psr.hip, plf_psr_prot.hip): pick
+// plf_prot_valu_exact.hip, plf_edge.hip, plf_psr.hip, plf_psr_prot.hip,
+// plf_psr_prot_mfma.hip, plf_psr_branch.hip): pick
 // a grid, pick a kernel instantiation, launch.
 // Internal to libplfx; no device code.
 #pragma once

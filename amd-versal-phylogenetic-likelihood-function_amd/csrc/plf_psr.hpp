@@ -706,6 +706,7 @@ struct PsrTileBatch {
   PsrTileDesc d[kMaxBatch];
 };
 
+#ifndef PLFX_PSR_NO_TILE_KERNEL  // a translation unit that only borrows this header's device functions
 __global__ void __launch_bounds__(kBlock)
 psr_tile_kernel(const PsrTileBatch tips, int count, int64_t n, int G, uint8_t *__restrict__ cat) {
   const int64_t total = (int64_t)G * n;
@@ -718,6 +719,7 @@ psr_tile_kernel(const PsrTileBatch tips, int count, int64_t n, int G, uint8_t *_
     else d.dst[v] = d.src[v - g * n];
   }
 }
+#endif
 
 }  // namespace dev
 }  // namespace plfx

@@ -19,6 +19,7 @@
 #include "../../include/plfx.h"
 #include "edge_newton.hpp"
 #include "plf_kernels.hpp"
+#include "branch_plan.hpp"
 #include "psr_edge_lower.hpp"
 #include "psr_lower.hpp"
 #include "psr_scan_lower.hpp"
@@ -64,6 +65,7 @@ struct plfx_ctx {
   plfx::PsrLaunchList psr_lowered;  // the same for plfx_plf_psr_dev and plfx_traverse_psr
   plfx::PsrEdgeLaunchList psr_edges_lowered;  // and for plfx_edge_sumtable_psr_batch
   plfx::PsrScanPlan psr_scan;       // and for plfx_psr_rate_scan
+  plfx::BranchPlan branches;        // and for plfx_branch_sumtables_psr
   // grow-only staging for the synchronous host entry points
   void *d_buf = nullptr;
   size_t d_cap = 0;
@@ -1432,6 +1434,83 @@ int plfx_edge_optimize_psr_dev_gen(plfx_ctx *ctx, int dtype, int states, const v
                             w->edge_state, w->lnl_partials, w->ws, t_opt + g, out3 ? out3 + 3 * (size_t)g : nullptr,
                             evals ? evals + g : nullptr, ctx->max_blocks, s);
       });
+}
+
+// ---- (13) all-branch derivatives of a PSR tree ----
+
+int plfx_branch_pair_sites_per_lane(int dtype) {
+  return dtype == PLFX_F32 || dtype == PLFX_F64 ? plfx::psr_branch_sites_per_lane(dtype) : 0;
+}
+
+int plfx_branch_sumtables_psr_workspace(int dtype, int states, int nops, int64_t n, size_t *bytes) {
+  if (int rc = check_psr_states(nullptr, states); rc != PLFX_OK) return rc;
+  plfx::BranchLayout lay;
+  if (!bytes || plfx::branch_layout(dtype, states, nops, n, &lay) != PLFX_OK) return PLFX_ERR_INVALID;
+  *bytes = lay.bytes;
+  return PLFX_OK;
+}
+
+int plfx_branch_sumtables_psr(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                              void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
+                              int npmats, const void *root_pmat, const void *EV, int64_t n,
+                              const uint8_t *rate_cat, int ncat, const int32_t *wgt, const int64_t *scaler_sums,
+                              const void *tipvec, void *workspace, size_t workspace_bytes, void **sumtabs_out,
+                              int64_t *edge_scale, void *stream) {
+  PLFX_BIND(ctx);
+  if (int rc = check_psr_states(ctx, states); rc != PLFX_OK) return rc;
+  if (flags & ~(PLFX_FMA | PLFX_BRANCH_NOFUSE))
+    return fail(ctx, PLFX_ERR_INVALID, "branch_sumtables_psr: bad flags %d", flags);
+  int mode;  // the W nodes run in the mode plfx_traverse_psr_ex runs the ops in, and are refused as there
+  if (int rc = check_psr_flags(ctx, "branch_sumtables_psr", dtype, states, flags & PLFX_FMA, &mode); rc != PLFX_OK)
+    return rc;
+  if (!sumtabs_out) return fail(ctx, PLFX_ERR_INVALID, "branch_sumtables_psr: null sumtabs_out");
+  // plan: the tree, the call, every node and table checked, every descriptor filled, before the first launch
+  plfx::BranchPlan &pl = ctx->branches;
+  const plfx::BranchCall call{dtype, states,   flags,        ops,         nops,   clv,       tips,
+                              nslots, pmats,   npmats,       root_pmat,   EV,     n,         rate_cat,
+                              ncat,   scaler_sums, tipvec,   workspace,   workspace_bytes,   edge_scale};
+  std::string err;
+  if (plfx::plan_branches(call, &pl, &err) != PLFX_OK) return fail(ctx, PLFX_ERR_INVALID, "%s", err.c_str());
+  hipStream_t s = pick(stream);
+  if (n == 0) {  // nothing to launch
+    if (int rc = zero_sums(ctx, s, edge_scale, 2 * nops); rc != PLFX_OK) return rc;
+    std::copy(pl.tab.begin(), pl.tab.end(), sumtabs_out);
+    return PLFX_OK;
+  }
+  PLFX_WS(ctx, s, w);
+  std::copy(pl.tab.begin(), pl.tab.end(), sumtabs_out);
+  static_assert(2 * plfx::kMaxPairs <= kWsRegions, "two ticket regions per sibling pair");
+  int64_t *wsum = reinterpret_cast<int64_t *>(static_cast<char *>(workspace) + pl.lay.cnt_off);
+  for (const plfx::BranchLaunch &it : pl.items) {
+    hipError_t e = hipErrorInvalidValue;
+    switch (it.kind) {
+      case plfx::kBranchPairs:
+        e = plfx::launch_psr_branch_pairs(dtype, it.tips, &pl.pairs[it.first], it.count, EV, rate_cat, ncat, wgt, n,
+                                          tipvec, w->ws, ctx->max_blocks, s);
+        break;
+      case plfx::kBranchNodes:
+        if (states == 20)
+          e = mode ? plfx::launch_plf_psr_prot_mfma(it.tips, &pl.nodes[it.first], it.count, EV, rate_cat, ncat, wgt, n,
+                                                    tipvec, w->ws, ctx->max_blocks, s)
+                   : plfx::launch_plf_psr_prot(dtype, it.tips, &pl.nodes[it.first], it.count, EV, rate_cat, ncat, wgt,
+                                               n, tipvec, w->ws, ctx->max_blocks, s);
+        else
+          e = plfx::launch_plf_psr(dtype, it.tips, &pl.nodes[it.first], it.count, EV, rate_cat, ncat, wgt, n, tipvec,
+                                   w->ws, ctx->max_blocks, s);
+        break;
+      case plfx::kBranchTables:
+        e = (states == 4 ? plfx::launch_edge_sumtable_psr_batch : plfx::launch_edge_sumtable_psr_prot_batch)(
+            dtype, it.tips != 0, &pl.edges[it.first], it.count, n, tipvec, ctx->max_blocks, s);
+        break;
+      case plfx::kBranchSub:
+      case plfx::kBranchScale:
+        e = plfx::launch_psr_branch_counts(it.kind == plfx::kBranchScale, &pl.scale[it.first], it.first, it.count,
+                                           scaler_sums, wsum, pl.sub, pl.outer, edge_scale, s);
+        break;
+    }
+    if (e != hipSuccess) return hip_fail(ctx, e, "branch_sumtables_psr launch");
+  }
+  return PLFX_OK;
 }
 
 // ---- (12) the PSR rate scan; (12b) the same with a state count ----

@@ -64,6 +64,7 @@ EXPORTS = (
     "plfx_edge_optimize_psr_gen", "plfx_edge_optimize_psr_dev_gen",
     "plfx_site_lnl_psr_gen", "plfx_psr_rate_scan_gen", "plfx_psr_rate_scan_workspace_gen",
     "plfx_plf_psr_dev_ex", "plfx_traverse_psr_ex", "plfx_psr_rate_scan_ex",
+    "plfx_branch_sumtables_psr", "plfx_branch_sumtables_psr_workspace", "plfx_branch_pair_sites_per_lane",
 )
 EDGE_MAX_EVALS = 256  # PLFX_EDGE_MAX_EVALS
 PSR_MAX_CATS = 32     # PLFX_PSR_MAX_CATS
@@ -77,8 +78,10 @@ PMAT_STATE, PMAT_EIGEN = 0, 1
 EXACT, FMA = 0, 1
 VALU = 2  # with FMA: protein f64 on the VALU (not the matrix cores): P and EV as wave-uniform scalar
           # operands, LDS holds only the staged child tile
+BRANCH_NOFUSE = 4  # PLFX_BRANCH_NOFUSE: branch_sumtables_psr lowers every op unfused
 PROT_CODES = 24  # protein tip codes: rows of the tip-vector table (plfx.h section 8)
 CTX_LAZY_TABLES = 1  # PLFX_CTX_LAZY_TABLES
+LOG_MINLIK = -22.18070977791824990137  # log(2^-32): one rescale's share of a log-likelihood (plf_lnl.hpp kLogMinLik)
 
 
 class PlfxError(RuntimeError):
@@ -219,6 +222,11 @@ def load():
     for name in ("plfx_plf_psr_dev", "plfx_traverse_psr", "plfx_psr_rate_scan"):
         base = getattr(L, name + "_gen").argtypes
         getattr(L, name + "_ex").argtypes = base[:3] + [i32] + base[3:]
+    # all-branch derivatives (section 13)
+    L.plfx_branch_sumtables_psr_workspace.argtypes = [i32, i32, i32, i64, C.POINTER(C.c_size_t)]
+    L.plfx_branch_sumtables_psr.argtypes = [vp, i32, i32, i32, top, i32, pvp, pvp, i32, vp, i32, vp, vp, i64, vp, i32,
+                                            vp, vp, vp, vp, C.c_size_t, pvp, vp, vp]
+    L.plfx_branch_pair_sites_per_lane.argtypes = [i32]
     L.plfx_psr_categorize.argtypes = [dp, i32, vp, vp, i64, i32, vp, dp, C.POINTER(i32), dp]
     L.plfx_psr_site_order.argtypes = [vp, i64, i32, vp]
     _lib = L
@@ -970,6 +978,76 @@ class Context:
         self._optimize_branches(True, True, states, sumtabs, n, eigen, rates, rate_cat, wgt, t0, t_opt, tmin, tmax,
                                 max_evals, out3, evals, stream)
 
+    # -- (13) all-branch derivatives of a per-site-rate tree ------------------
+    def branch_sumtables_psr(self, states, ops, clv, pmats, root_pmat, EV, n, rate_cat, ncat, scaler_sums, workspace,
+                             wgt=None, edge_scale=None, tips=None, tipvec=None, fma=False, nofuse=False,
+                             stream=None):
+        """The outer CLVs and the sum table of every branch of the tree that
+        traverse_psr_gen(states, ops, clv, pmats, ...) has just run
+        (plfx_branch_sumtables_psr, plfx.h section 13).  root_pmat: ncat *
+        states^2 values, pmatrix() of the joined root length; scaler_sums: the
+        traversal's (int64, one per op; may be None without edge_scale);
+        workspace: a uint8 device tensor of branch_sumtables_psr_workspace()
+        bytes; edge_scale: optional int64 device tensor of 2 * nops counts.
+        Returns the 2 * nops sum tables, edge 2*j + s = op j's child s, as
+        views of the workspace (the root op's two entries are one table),
+        ready for optimize_branches_psr_gen.  nofuse: PLFX_BRANCH_NOFUSE."""
+        import torch
+
+        S = self._psr_states(True, states)
+        n, ncat = int(n), int(ncat)
+        dt = EV.dtype
+        if dt not in (torch.float32, torch.float64):
+            raise PlfxError(ERR_INVALID, f"unsupported dtype {dt}")
+        top, nops, slots, tp, nslots, npmats, _ = self._traverse_args(
+            ops, clv, pmats, EV, n, wgt, None, scaler_sums, tips, S, S * S * max(ncat, 1), S * S)
+        _tensor(rate_cat, "rate_cat", torch.uint8, n)
+        _tensor(root_pmat, "root_pmat", dt, S * S * max(ncat, 1))
+        _tensor(edge_scale, "edge_scale", torch.int64, 2 * nops, optional=True)
+        _tensor(workspace, "workspace", torch.uint8, 0)
+        tabs = (C.c_void_p * max(1, 2 * nops))()
+        flags = (FMA if fma else 0) | (BRANCH_NOFUSE if nofuse else 0)
+        self._check(self._L.plfx_branch_sumtables_psr(
+            self.h, F32 if dt == torch.float32 else F64, S, flags, top, nops, slots, tp, nslots, _ptr(pmats), npmats,
+            _ptr(root_pmat), _ptr(EV), n, _ptr(rate_cat), ncat, _ptr(wgt), _ptr(scaler_sums),
+            self._tipvec(tipvec, dt, S), _ptr(workspace), workspace.numel(), tabs, _ptr(edge_scale),
+            self._sh(stream)))
+        base, nbytes = workspace.data_ptr(), S * n * (4 if dt == torch.float32 else 8)
+        return [workspace[(tabs[e] or base) - base:(tabs[e] or base) - base + nbytes].view(dt) for e in range(2 * nops)]
+
+    def branch_derivatives_psr(self, states, ops, clv, pmats, root_pmat, EV, n, rate_cat, ncat, scaler_sums, workspace,
+                               eigen, rates, blen, wgt=None, tips=None, tipvec=None, fma=False, nofuse=False,
+                               tmin=1e-8, tmax=10.0, stream=None):
+        """lnL, d lnL/dt and d2 lnL/dt2 of EVERY branch at its current length:
+        branch_sumtables_psr() and then one evaluation of the device loop
+        (optimize_branches_psr_gen with max_evals=1 from the current lengths,
+        which stores its sums at the evaluated t, clamped into [tmin, tmax]).
+        blen: the 2 * npmats branch lengths that made pmats (host values);
+        edge 2*j + s has blen[2 * ops[j].pmat + s], the root op's two edges the
+        sum of its two.  Returns (lnl, d1, d2), float64 device tensors of
+        2 * nops, lnl with the edge's scaling correction
+        edge_scale * log(2^-32) applied.  Asynchronous."""
+        import torch
+
+        rows = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
+        nops = rows.shape[0]
+        bl = np.asarray(blen, dtype=np.float64).reshape(-1)
+        t = np.array([bl[2 * rows[j, 3] + s] for j in range(nops) for s in (0, 1)], dtype=np.float64)
+        if nops:
+            t[-2:] = t[-2] + t[-1]
+        dev = workspace.device
+        scale = torch.zeros(2 * nops, dtype=torch.int64, device=dev)
+        tabs = self.branch_sumtables_psr(states, ops, clv, pmats, root_pmat, EV, n, rate_cat, ncat, scaler_sums,
+                                         workspace, wgt=wgt, edge_scale=scale, tips=tips, tipvec=tipvec, fma=fma,
+                                         nofuse=nofuse, stream=stream)
+        t0 = torch.from_numpy(t).to(dev)
+        t_opt = torch.empty(2 * nops, dtype=torch.float64, device=dev)
+        out3 = torch.empty(3 * 2 * nops, dtype=torch.float64, device=dev)
+        self.optimize_branches_psr_gen(states, tabs, n, eigen, rates, rate_cat, t0, t_opt, tmin=tmin, tmax=tmax,
+                                       max_evals=1, out3=out3, wgt=wgt, stream=stream)
+        o = out3.view(-1, 3)
+        return o[:, 0] + scale.to(torch.float64) * LOG_MINLIK, o[:, 1], o[:, 2]
+
     # -- (12) the PSR rate scan ----------------------------------------------
     def site_lnl_psr(self, x, n, site_lnl, freq=None, scalers=None, nsc=None, stride=None, states=4, stream=None):
         """Per-site lnL of a per-site-rate CLV with the site's own scaling
@@ -1240,6 +1318,21 @@ def psr_rate_scan_workspace(dtype, nops, ntips, npmats, n, group=PSR_MAX_CATS):
     _host_check(load().plfx_psr_rate_scan_workspace(_scan_dtype(dtype), int(nops), int(ntips), int(npmats), int(n),
                                                     int(group), C.byref(out)), "psr_rate_scan_workspace")
     return int(out.value)
+
+
+def branch_sumtables_psr_workspace(dtype, states, nops, n):
+    """Bytes of the workspace Context.branch_sumtables_psr() needs (plfx.h
+    section 13): the outer CLVs, the 2 * nops - 1 tables and the counters.
+    dtype: F32 / F64, a numpy dtype or a torch dtype."""
+    out = C.c_size_t(0)
+    _host_check(load().plfx_branch_sumtables_psr_workspace(_scan_dtype(dtype), int(states), int(nops), int(n),
+                                                           C.byref(out)), "branch_sumtables_psr_workspace")
+    return int(out.value)
+
+
+def branch_pair_sites_per_lane(dtype):
+    """Sites per lane and trip of the fused sibling-pair kernel (plfx_branch_pair_sites_per_lane)."""
+    return int(load().plfx_branch_pair_sites_per_lane(_scan_dtype(dtype)))
 
 
 def psr_rate_scan_workspace_gen(dtype, states, nops, ntips, npmats, n, group=PSR_MAX_CATS):

@@ -1133,6 +1133,94 @@ int plfx_psr_rate_scan_ex(plfx_ctx *ctx, int dtype, int states, int flags, const
                           size_t workspace_bytes, int32_t *best_idx, double *best_lnl, double *all_lnl,
                           double *out_lnl, void *stream);
 
+/* ---- (13) all-branch derivatives of a PSR tree: outer CLVs and the sum table
+ * of every branch in one call (extension) -------------------------------------
+ * Sections (11) / (11c) differentiate the one branch between two CLVs the
+ * caller holds, and a traversal only makes post-order CLVs: the branch the
+ * tree is rooted on.  This section makes, for EVERY branch, the CLV of
+ * everything outside the subtree below it and the branch's sum table, ready
+ * for plfx_edge_optimize_psr_dev_gen / plfx_edge_derivatives_psr_gen.
+ *
+ * INPUT.  A post-order op list ops[0..nops) of ONE rooted binary tree after
+ * plfx_traverse_psr_ex has run on it with the same ops, clv, tips, nslots,
+ * pmats, npmats, EV, n, rate_cat, ncat, wgt and tipvec: clv[] and
+ * scaler_sums[0..nops) are inputs here, and no byte of clv[] is written.
+ * The CLVs must be in the eigen convention of section (10).
+ *
+ * TREE RULES (else PLFX_ERR_INVALID): every parent slot is written once; every
+ * written slot but the last op's parent is read by exactly one later op; no
+ * slot is read twice; the last op is the root op; a slot that no op writes is
+ * a tip, dense (clv[slot]) or coded (tips[slot]), and only read; the root
+ * op's two children are not both coded tips.
+ *
+ * EDGES.  Edge e = 2*j + s is the branch of op j to its child s (0 = child1 /
+ * left, 1 = child2 / right); its length is the one blen[2*ops[j].pmat + s]
+ * that made the op's matrix.  The root op's two branches are ONE edge of the
+ * summed length: both of its entries carry the same table and the same count.
+ *
+ * OUTER CLV W(c), for a child c of op j: the PSR CLV of everything outside
+ * c's subtree, located at c's parent node.
+ *   root op (r, a, b):  W(a) is slot b itself and W(b) slot a; nothing is copied.
+ *   op j = (v, c1, c2): W(c1) = node(x1 = W(v), left = Pup(v), x2 = slot c2, right = op j's right matrix)
+ *                       W(c2) = node(x1 = W(v), left = Pup(v), x2 = slot c1, right = op j's left matrix)
+ *   Pup(v) is the matrix of v's branch in the op that reads v -- or, when that
+ *   op is the root op, root_pmat: ncat * states^2 values the caller makes with
+ *   plfx_pmatrix for the joined root length (both root branches summed).
+ * Each W is bit for bit what a one-node plfx_plf_psr_dev_ex call with those
+ * arguments and the call's flags writes, the 2^-32 rescale and the node's
+ * weighted scaler sum included.
+ *
+ * SUM TABLE of edge e to child c: plfx_edge_sumtable_psr_gen(side 1 = slot c,
+ * dense or coded; x2 = W(c)) bit for bit; the root edge is x_a * x_b with a
+ * coded child as side 1.  A coded tip anywhere needs tipvec.
+ *
+ * edge_scale[e] (device int64[2*nops], may be NULL): the scaler count of edge
+ * e's lnL -- scaler_sums over c's subtree, the sums of every W on the way up
+ * (W(c)'s own, W(v)'s, ...) and scaler_sums of the sibling subtrees hanging
+ * off that path: lnL(e) = out3[0] + edge_scale[e] * log(2^-32).  Integer sums,
+ * formed on the device.  NULL: no count is formed, scaler_sums is not read.
+ *
+ * SCHEDULE.  The ops are levelled by depth from the root op; level by level,
+ * an op with 4 states and a dense W(v) runs as ONE fused sibling-pair launch
+ * (up to 16 ops each) that reads W(v) and both children once and writes both
+ * W and both tables; every other op (20 states; PLFX_BRANCH_NOFUSE; W(v) a
+ * coded tip, which happens only under a root child whose sibling is coded) as
+ * plfx_plf_psr_dev_ex batches followed by plfx_edge_sumtable_psr_batch_gen
+ * launches.  The W of a coded child exists only for its table: unfused it has
+ * a slab of the workspace, fused it is never written.  Results are the same
+ * bits whatever the schedule.
+ *
+ * flags: 0, PLFX_FMA (20 states: the W nodes in the mode plfx_traverse_psr_ex
+ * runs them in; refused as there), PLFX_BRANCH_NOFUSE; any other bit is
+ * PLFX_ERR_INVALID.  states: 4 or 20, else PLFX_ERR_UNSUPPORTED.
+ *
+ * The workspace (device, 256-byte aligned, >= plfx_branch_sumtables_psr_workspace
+ * bytes) holds slabs of slab = n * states * sizeof(dtype) rounded up to 256
+ * bytes: W of edge e < 2*(nops-1) at byte e * slab (readable after the call;
+ * a coded child's is scratch or untouched), then the 2*nops - 1 tables, then
+ * the counters, int64: the weighted scaler sum of W of edge e at counter e,
+ * written when edge_scale is given.  It must share no byte with a slot.
+ * sumtabs_out: HOST array of 2*nops device pointers into the workspace, filled
+ * before the call returns.  Asynchronous, allocates nothing, descriptors in
+ * the kernel arguments, capture-safe.  Every check runs before the first
+ * launch: a refused call enqueues nothing and leaves sumtabs_out as it was.
+ * n == 0: nothing is launched and edge_scale is zeroed.  After branch lengths
+ * change the caller re-runs the traversal and this call. */
+#define PLFX_BRANCH_NOFUSE 4
+
+int plfx_branch_sumtables_psr_workspace(int dtype, int states, int nops, int64_t n, size_t *bytes);
+
+int plfx_branch_sumtables_psr(plfx_ctx *ctx, int dtype, int states, int flags, const plfx_trav_op *ops, int nops,
+                              void *const *clv, const uint8_t *const *tips, int nslots, const void *pmats,
+                              int npmats, const void *root_pmat, const void *EV, int64_t n,
+                              const uint8_t *rate_cat, int ncat, const int32_t *wgt, const int64_t *scaler_sums,
+                              const void *tipvec, void *workspace, size_t workspace_bytes, void **sumtabs_out,
+                              int64_t *edge_scale, void *stream);
+
+/* Sites per lane and trip of the fused sibling-pair kernel (dtype PLFX_F32 /
+ * PLFX_F64; 0 for anything else): a block covers 256 times as many sites. */
+int plfx_branch_pair_sites_per_lane(int dtype);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
